@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json headline: scanned rows/s + HBM GB/s on the C3
 workload (100M-row 4 x int32 Columnarfile, 2-predicate conjunction + COUNT),
-at 1 / 2 / 4 / 8 GPUs, plus one record per other BASELINE config (C2, C4, C5).
+at 1 / 2 / 4 / 8 GPUs; with --full, plus one record per other BASELINE config
+(C2, C4, C5).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline
+needs and no more: it sets the table up, verifies one step, warms up, times
+EXACTLY K steps, writes the last step's outputs if --dump-outputs DIR is given
+(DIR/count.npy: the query's COUNT, float64; the table comes from fixed seeds,
+so the same arguments give the same inputs and outputs in every run) and
+prints the line (`ms_per_step` = the wall time of the K steps / K, in ms).
+Everything else is measured only with --full: the scan kernel's own time and
+the roofline record, the read probe, the config records, the CPU baseline
+and, at N > 1, the strong and bucketed sub-records; without it the line
+carries `roofline`, `cpu_baseline`, `bucketed`, `strong`: null, `configs`: {}.
 
 One "step" = one ColumnarFileScan COUNT pass over the resident table:
 `query ... {(c0 < 2^19)} ^ {(c1 >= 2^19)} FILESCAN` -> Total Results Count
@@ -18,8 +30,8 @@ range with no data-path collective and one exchange per query, so the
 headline reports weak scaling:
   --scaling weak (default): per-GPU work fixed at the C3 table -- rank r owns
       rows [r * 100M, (r + 1) * 100M) of an N x 100M-row logical table (its own
-      seeds 42 + 1000 r + col; N = 1 is exactly the C3 table).  At N > 1 the
-      same run also times the STRONG form and reports it as the `strong`
+      seeds 42 + 1000 r + col; N = 1 is exactly the C3 table).  At N > 1 a
+      --full run also times the STRONG form and reports it as the `strong`
       sub-record: the metric's ONE 100M-row table in N 64-aligned shards
       (mbx_shard_bounds), with its phases (scan max over ranks, exchange).
       Both forms are also timed with the COUNTs of each captured graph's
@@ -33,12 +45,12 @@ COUNT, every count-frame arrival): a broken collective or frame decode exits
 non-zero with a one-line reason before any timed work (`pre_check`).
 value = global rows scanned by all ranks / max-over-ranks wall time.
 
-Kernel time (`roofline.kernel_ms`, every config's `kernel_ms`): one captured
+Kernel time (--full: `roofline.kernel_ms`, every config's `kernel_ms`): one captured
 HIP graph of --kernel-graph launches of the query's kernels alone, replayed,
 HIP events on the library stream around the replays / launches -- so
 kernel_ms <= ms_per_step (no per-launch event pair).
 
-Config records (`configs`, --configs, default C5,C4,C2 -- C5 first, on the
+Config records (--full: `configs`, --configs, default C5,C4,C2 -- C5 first, on the
 heap C3 leaves, profiles/r05/m):
   C2  10M rows x 4 int32, c0 < 104858 -> BitSet + positions + COUNT, one
       launch (k_scan_select); a 1-GPU config: rank 0 only
@@ -55,10 +67,11 @@ Each is checked against torch reductions of the same device data before
 and after its timing.  stdout carries only the JSON line.  A rank still
 running --watchdog seconds (420) after its imports prints its threads'
 tracebacks and exits 1 (the backstop behind the per-phase deadlines).
-cpu_baseline (N = 1, rank 0): the oracle over the GPU run's own C3 table,
+cpu_baseline (--full, N = 1, rank 0): the oracle over the GPU run's own C3 table,
 copied to host after timing; its COUNT must equal the GPU's.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--configs C2,C4,C5|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--scaling strong|weak]
+                    [--full [--configs C2,C4,C5|none]]
 
 Launch: with WORLD_SIZE unset and --gpus N > 1, this process is only a
 launcher: before anything touches a GPU it starts N rank ("worker")
@@ -593,6 +606,11 @@ def make_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: kernel time and roofline, read probe, the config records (--configs), "
+                         "the CPU baseline and, at N > 1, the strong and bucketed sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--rows", type=int, default=100_000_000,
                     help="global rows (strong scaling) or rows per GPU (weak)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="weak")
@@ -954,16 +972,23 @@ def run_c3(H, args, cols, n, s, glob, label, bucket=None):
                                  reset=lambda: (counts.zero_(), torch.cuda.synchronize()), verify=verify, label=label)
     reason = verify(warmup, warmup + steps, f"{label} timed steps")
     H.agree(reason)
+    # what the caller of the last timed step receives: its COUNT (global with an
+    # exchange), decoded from the step's frame where the steps write frames
+    last = counts[warmup + steps - 1].cpu().numpy()
+    last_count = int(frame_fields(last)[0][0]) if frames else int(last[0])
 
-    # kernel duration: a graph of --kernel-graph scans alone (own scratch slots)
-    KG = max(1, args.kernel_graph)
-    scratch = torch.zeros((KG, FW), dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-    kern_ms, kern_max = H.kernel_ms(lambda i: scan(i, scratch.data_ptr()), KG)
+    # kernel duration (--full): a graph of --kernel-graph scans alone (own scratch slots)
+    kern_ms = kern_max = None
+    if args.full:
+        KG = max(1, args.kernel_graph)
+        scratch = torch.zeros((KG, FW), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        kern_ms, kern_max = H.kernel_ms(lambda i: scan(i, scratch.data_ptr()), KG)
     print(f"rank {rank}: {label} rows [{s}, {s + n}), host enqueue {enq_us:.1f} us/step, "
-          f"wall {ms_step * 1e3:.1f} us/step, scan kernel {kern_ms * 1e3:.1f} us (graph of {KG})", file=sys.stderr)
+          f"wall {ms_step * 1e3:.1f} us/step"
+          + (f", scan kernel {kern_ms * 1e3:.1f} us (graph of {KG})" if args.full else ""), file=sys.stderr)
     return dict(table=table, plan=plan, frames=frames, ms_step=ms_step, enq_us=enq_us, G=G, B=B,
-                kern_ms=kern_ms, kern_max=kern_max, want=want)
+                kern_ms=kern_ms, kern_max=kern_max, want=want, last_count=last_count)
 
 
 def timing_label(G, steps):
@@ -1247,11 +1272,26 @@ def bucketed_record(r, rows, exchange="one RCCL all-reduce of the COUNT frames o
             "exchange": exchange}
 
 
+def dump_outputs(path, r):
+    """--dump-outputs: what the caller of the last timed C3 step received, one
+    .npy per output: `count` = that query's Total Results Count (the global
+    COUNT after the exchange at N > 1), float64 (exact: a COUNT is < 2^53).
+    The table comes whole from fixed seeds, so the same arguments give the
+    same inputs in every run and two builds compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "count.npy"), np.array([r["last_count"]], dtype=np.float64))
+
+
 def main():
     args = make_parser().parse_args()
     if args.gpus < 1:
         print(f"bench: --gpus {args.gpus}", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print(f"bench: --steps {args.steps} --warmup {args.warmup}", file=sys.stderr)
+        sys.exit(2)
+    full = args.full
 
     configs = [c.strip().upper() for c in args.configs.split(",") if c.strip() and c.strip().lower() != "none"]
     bad = [c for c in configs if c not in ("C2", "C4", "C5")]
@@ -1373,12 +1413,16 @@ def main():
     if glob is None and exchange:  # weak: the sum of every rank's own torch count
         glob = H.rsum(int(((cols[0] < THRESH) & (cols[1] >= THRESH)).sum().item()))
     r3 = run_c3(H, args, cols, n, s, glob, "C3")
-    arm("read probe", PHASE_S["probe"])
-    probe = read_probe(H, r3["table"]) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r3)
+    probe = None
+    if full and rank == 0:
+        arm("read probe", PHASE_S["probe"])
+        probe = read_probe(H, r3["table"])
     # the CPU baseline scans THIS table (the GPU run's arrays): one
     # device -> host copy of the 4 columns, outside every timed region
     host_cols = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         host_cols = [c.cpu().numpy() for c in cols]
     r3["table"].close()
     r3["plan"].close()
@@ -1387,7 +1431,7 @@ def main():
     # captured graph's steps sharing ONE all-reduce: the throughput form for a
     # stream of queries (xGMI collectives cost their latency, not their bytes)
     bucketed = None
-    if bucketed_form(args, world, exchange):
+    if full and bucketed_form(args, world, exchange):
         rb = run_c3(H, args, cols, n, s, glob, "C3 bucketed", bucket=args.graph_steps)
         rb["table"].close()
         rb["plan"].close()
@@ -1398,7 +1442,7 @@ def main():
 
     # ---- strong sub-record at N > 1: the metric's ONE 100M-row table ----------
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_strong:
+    if full and world > 1 and args.scaling == "weak" and not args.no_strong:
         ss, se = m.mbx.shard_bounds(args.rows, world, rank)
         scols = make_columns(torch, args.rows, ss, se, 42)
         sglob = full_count(torch, args.rows, 42)
@@ -1425,7 +1469,7 @@ def main():
 
     # ---- the other BASELINE configs ------------------------------------------
     crecs = {}
-    for name in configs:
+    for name in configs if full else []:
         arm(f"config {name}", PHASE_S["config"])
         if name == "C2":
             if rank == 0:
@@ -1441,7 +1485,36 @@ def main():
         ms_per_step = r3["ms_step"]
         kern_ms, kern_max, frames = r3["kern_ms"], r3["kern_max"], r3["frames"]
         algo_bytes = 2 * 4 * n  # c0 + c1 read once per launch (rank 0's shard)
-        achieved = algo_bytes / (kern_ms * 1e-3) / 1e9
+        phases = {"step_wall": ms_per_step * 1e3, "host_enqueue_rank0": r3["enq_us"]}
+        roofline = None
+        if full:  # the scan kernel's own time and the read probe took runs of their own
+            achieved = algo_bytes / (kern_ms * 1e-3) / 1e9
+            phases = {
+                "step_wall": ms_per_step * 1e3,
+                "scan_kernel_max_over_ranks": kern_max * 1e3,
+                "host_enqueue_rank0": r3["enq_us"],
+                "exchange_and_overlap": max(0.0, ms_per_step * 1e3 - kern_max * 1e3),
+            }
+            roofline = {
+                "bound": "hbm",
+                "kernel": "mbx::k_scan_fast<2, COUNT, no-deleted>",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "traffic": load_traffic(n, "frame" if frames else "finalize"),
+                "traffic_unit": "HBM bytes per launch of rank 0's shard scan (rocprofv3 PMC, "
+                                "profiles/c3_scan_pmc.json, same rows and COUNT form)",
+                "kernel_ms": kern_ms,
+                "kernel_timing": f"one HIP graph of {max(1, args.kernel_graph)} scans replayed 3 times, HIP events "
+                                 "on the library stream / launches",
+                "algorithmic_bytes_per_launch": algo_bytes,
+                # secondary denominator (SURVEY 8(d)): the best read rate of the
+                # scan's own load pattern with the predicate removed
+                "measured_read_peak": probe["best_gbs"],
+                "frac_of_measured_read_peak": achieved / probe["best_gbs"],
+                "read_probe": probe,
+            }
         B = r3["B"]
         xchg = ((f"RCCL all-reduce of the COUNTs of every {B} steps (libmbx mbx_comm, after the scans)" if B > 1
                  else "RCCL all-reduce of every step's COUNT (one collective per query; libmbx mbx_comm, right "
@@ -1482,33 +1555,10 @@ def main():
             "pre_check": "ok: one exchanged step verified on every rank before timing" if exchange else
                          "ok: one step verified before timing",
             "exchange_form": exchange_form(r3["G"], fallback, host_reason),
-            "phases_us": {
-                "step_wall": ms_per_step * 1e3,
-                "scan_kernel_max_over_ranks": kern_max * 1e3,
-                "host_enqueue_rank0": r3["enq_us"],
-                "exchange_and_overlap": max(0.0, ms_per_step * 1e3 - kern_max * 1e3),
-            },
+            "phases_us": phases,
             "hbm_gbs": 2 * 4 * n_global / (ms_per_step * 1e-3) / 1e9,
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "mbx::k_scan_fast<2, COUNT, no-deleted>",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": load_traffic(n, "frame" if frames else "finalize"),
-                "traffic_unit": "HBM bytes per launch of rank 0's shard scan (rocprofv3 PMC, "
-                                "profiles/c3_scan_pmc.json, same rows and COUNT form)",
-                "kernel_ms": kern_ms,
-                "kernel_timing": f"one HIP graph of {max(1, args.kernel_graph)} scans replayed 3 times, HIP events "
-                                 "on the library stream / launches",
-                "algorithmic_bytes_per_launch": algo_bytes,
-                # secondary denominator (SURVEY 8(d)): the best read rate of the
-                # scan's own load pattern with the predicate removed
-                "measured_read_peak": probe["best_gbs"],
-                "frac_of_measured_read_peak": achieved / probe["best_gbs"],
-                "read_probe": probe,
-            },
+            "full": full,
+            "roofline": roofline,
             "bucketed": bucketed,
             "strong": strong,
             "configs": crecs,

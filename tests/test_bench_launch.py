@@ -89,11 +89,13 @@ def _bench_module():
 
 
 def test_default_run_adds_every_config_record():
-    """The driver's plain `bench.py --gpus N` measures C2, C4 and C5 beside
-    the C3 headline, and every record carries CONFIG_KEYS
-    with kernel time from graph replay."""
+    """`bench.py --gpus N --full` measures C2, C4 and C5 beside the C3
+    headline with no further option, and every record carries
+    CONFIG_KEYS with kernel time from graph replay."""
     b = _bench_module()
-    a = b.make_parser().parse_args([])
+    assert not b.make_parser().parse_args([]).full
+    a = b.make_parser().parse_args(["--full"])
+    assert a.full and not a.no_cpu_baseline
     assert sorted(a.configs.split(",")) == ["C2", "C4", "C5"] and a.scaling == "weak" and not a.no_strong
     assert a.c4_rows == 100_000_000 and a.c5_rows == 125_000_000 and a.kernel_graph >= 10
     rec = b.config_record("C4", 100_000_000, 50_000_000, 2, 1_000_000, 0.040, "k", 0.030, 0.031, 33_000_000,
@@ -401,3 +403,44 @@ def test_every_shard_size_has_request_split_traffic():
         cfg = json.load(f)["configs"]
     for key in ("C2:10000000", "C4:100000000", "C5:125000000"):
         assert cfg[key]["read_basis"] == "request split", key
+
+
+# ---- the plain run, --full and --dump-outputs --------------------------------
+
+def test_dump_outputs_writes_the_last_count(tmp_path):
+    """--dump-outputs DIR: DIR/count.npy holds the last timed step's COUNT as
+    float64, exactly (the directory is created when missing)"""
+    import numpy as np
+    b = _bench_module()
+    out = tmp_path / "a" / "b"
+    b.dump_outputs(str(out), {"last_count": 24_998_113})
+    assert sorted(os.listdir(out)) == ["count.npy"]
+    a = np.load(out / "count.npy")
+    assert a.dtype == np.float64 and a.tolist() == [24_998_113.0]
+    a = b.make_parser().parse_args(["--dump-outputs", "x", "--steps", "7", "--warmup", "2"])
+    assert a.dump_outputs == "x" and a.steps == 7 and a.warmup == 2 and not a.full
+    assert run_bench(["--steps", "0"]).returncode == 2
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_count(tmp_path):
+    """A plain run over a small odd-sized table: the line's headline keys, K
+    timed steps, nothing that takes a run of its own, and count.npy equal to a
+    torch reduction over the same seeded columns (so every run of the same
+    arguments writes the same output)."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    n = 1_000_003
+    r = run_bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--rows", str(n), "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    x = _line(r.stdout)
+    assert x["metric"] == b.METRIC and x["unit"] == "rows/s" and x["higher_is_better"] is True
+    assert x["dtype"] == "int32" and x["steps"] == 7 and x["warmup"] == 2 and x["n_gpus"] == 1
+    assert x["ms_per_step"] > 0 and abs(x["value"] - n / (x["ms_per_step"] * 1e-3)) <= 1e-6 * x["value"]
+    assert x["full"] is False and x["roofline"] is None and x["cpu_baseline"] is None and x["configs"] == {}
+    c0 = b.gen_column(torch, n, 0, n, 42, 1 << 20)
+    c1 = b.gen_column(torch, n, 0, n, 43, 1 << 20)
+    want = int(((c0 < b.THRESH) & (c1 >= b.THRESH)).sum().item())
+    got = np.load(tmp_path / "count.npy")
+    assert got.dtype == np.float64 and got.tolist() == [float(want)] and 0 < want < n

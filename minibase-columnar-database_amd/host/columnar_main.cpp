@@ -17,6 +17,8 @@
 //                                                              (R/input/BitMapQuery.java:48-300)
 //   delete_query DBNAME COLUMNARFILENAME {C,OP,V} NUMBUF ACCESS md|pd
 //                                                              (R/input/DeleteQuery.java:28-215)
+//   sort DBNAME COLUMNARFILENAME [SORTCOLS] [PROJCOLS] ASC|DSC NUMBUF NUMBUF_SORT
+//                                                              (R/input/ColumnarSort.java:73-393)
 //   exit
 //
 // Output lines (column header, rows, "Total Results Count By Query: n")
@@ -713,6 +715,81 @@ void bmj_cmd(const std::vector<std::string>& a) {
   print_results_footer(n);
 }
 
+// one column's values at `pos` as the reference prints them (GPU gather by position)
+std::vector<std::string> column_text(const columnar::Columnarfile& cf, int col, const std::vector<int64_t>& pos) {
+  const int64_t n = (int64_t)pos.size();
+  const auto at = cf.getAttributeTypes()[(size_t)col].attrType;
+  const int w = at == AttrType::attrString ? cf.getAttrSizes()[(size_t)col] : 4;
+  std::vector<uint8_t> buf((size_t)std::max<int64_t>(n, 1) * (size_t)w);
+  void* outp = buf.data();
+  int32_t pc = col;
+  ok(mbx_gather(global::SystemDefs::ctx(), cf.table(), pos.data(), n, &pc, 1, &outp), "gather");
+  std::vector<std::string> text((size_t)n);
+  for (int64_t k = 0; k < n; k++) {
+    const uint8_t* v = buf.data() + (size_t)k * (size_t)w;
+    if (at == AttrType::attrInteger) {
+      int32_t x;
+      memcpy(&x, v, 4);
+      text[(size_t)k] = std::to_string(x) + " ";
+    } else if (at == AttrType::attrString) {
+      text[(size_t)k] = std::string((const char*)v, strnlen((const char*)v, (size_t)w)) + " ";
+    }  // attrReal: printDataOfGivenTupleWithoutPosition has no case for it (:733-736) -- nothing printed
+  }
+  return text;
+}
+
+// sort DB CF [SORTCOLS] [PROJCOLS] ASC|DSC NUMBUF NUMBUF_SORT (R/input/ColumnarSort.java:73-393).
+// Argument checks and messages as execute() :77-135.  Printed: `SORTED COLUMNS`,
+// one line per record -- every projected value and a space, then ':' and the
+// position (:434-499) -- the record count, and the tuple count footer.  Not
+// printed: the `HeapFilePrefix:` line (its number is random), the `PASS NO` /
+// `RunArray:` / `New Page IDs:` lines (page ids of run files that do not exist
+// here) and the page counters.  A one-page input is sorted like any other (the
+// reference has no result file for it and fails, :241-243,358).
+void sort_cmd(const std::vector<std::string>& a) {
+  if (a.size() < 8) throw std::runtime_error("Invalid number of attributes.");
+  if (!global::SystemDefs::exists(a[1])) throw std::runtime_error("Database does not exist.");
+  auto bracketed = [](const std::string& s) { return s.size() >= 2 && s.front() == '[' && s.back() == ']'; };
+  if (!bracketed(a[3])) throw std::runtime_error("[TARGETCOLUMNNAMES] format invalid.");
+  if (!bracketed(a[4])) throw std::runtime_error("[PROJECTIONCOLUMNNAMES] format invalid.");
+  bool descending;
+  if (a[5] == "ASC") descending = false;
+  else if (a[5] == "DSC") descending = true;
+  else throw std::runtime_error("This sorting order is not supported");
+  int numbuf = 0, numbuf_sort = 0;
+  try {
+    numbuf = std::stoi(a[6]);
+  } catch (...) {
+    throw std::runtime_error("NUMBUF is not integer.");
+  }
+  if (numbuf < 1) throw std::runtime_error("NUMBUF is not more than 1.");
+  try {
+    numbuf_sort = std::stoi(a[7]);
+  } catch (...) {
+    throw std::runtime_error("NUMBUF is not integer.");
+  }
+  if (numbuf_sort < 3) {
+    std::cout << "NUMBUF_SORT is less than 3. External Sort Merge needs minimum 3 pages for the operation\n";
+    return;
+  }
+  columnar::Columnarfile cf(global::SystemDefs::open(a[1], 0), a[2]);
+  std::vector<int> sort_cols, proj_cols;
+  for (auto& n : split(trim(a[4].substr(1, a[4].size() - 2)), ',')) proj_cols.push_back(cf.colNameToIndex(trim(n)));
+  for (auto& n : split(trim(a[3].substr(1, a[3].size() - 2)), ',')) sort_cols.push_back(cf.colNameToIndex(n));
+  const std::vector<int64_t> pos = input::ColumnarSort::sortedPositions(cf, sort_cols, descending, numbuf_sort);
+  std::vector<std::vector<std::string>> text;
+  for (int c : proj_cols) text.push_back(column_text(cf, c, pos));
+  std::cout << "SORTED COLUMNS\n";
+  std::string line;
+  for (size_t k = 0; k < pos.size(); k++) {
+    line.clear();
+    for (auto& t : text) line += t[k];
+    std::cout << line << ":" << pos[k] << "\n";
+  }
+  std::cout << pos.size() << "\n";
+  std::cout << "=======================EXTRA METAINFO===============================\n" << cf.getTupleCnt() << "\n";
+}
+
 }  // namespace
 
 int run() {
@@ -736,6 +813,7 @@ int run() {
       else if (a[0] == "delete_query") delete_query(a);
       else if (a[0] == "bmj") bmj_cmd(a);
       else if (a[0] == "columnsscan") columnsscan_cmd(a);
+      else if (a[0] == "sort") sort_cmd(a);
       else if (a[0] == "exit") break;
       else std::cout << "Command not supported by the GPU executor: " << a[0] << "\n";
     } catch (const std::exception& e) {

@@ -1355,4 +1355,27 @@ int ShardedColumnarIndexScan::getTupleSize() { return Jtuple_.size(); }
 
 }  // namespace index
 
+namespace input {
+
+std::vector<int64_t> ColumnarSort::sortedPositions(const columnar::Columnarfile& cf, const std::vector<int>& sortCols,
+                                                   bool descending, int numBufForSort) {
+  std::vector<mbx_sort_key> keys;
+  for (int c : sortCols) keys.push_back(mbx_sort_key{c, 0});
+  mbx_ctx* c = global::SystemDefs::ctx();
+  mbx_sort_result* r = nullptr;
+  // availableInputBuffer = numBufForSort - 1 pages per pass-0 group (:238-241)
+  chk<chainexception::ChainException>(mbx_sort(c, cf.table(), nullptr, keys.data(), (int32_t)keys.size(),
+                                        descending ? MBX_SORT_DSC : MBX_SORT_ASC, numBufForSort - 1, &r),
+                               "ColumnarSort");
+  int64_t n = 0;
+  mbx_sort_info(r, &n, nullptr, nullptr);
+  std::vector<int64_t> pos((size_t)n);
+  const int rc = mbx_sort_fetch(c, r, 0, n, pos.data());
+  mbx_sort_free(r);
+  chk<chainexception::ChainException>(rc, "ColumnarSort");
+  return pos;
+}
+
+}  // namespace input
+
 }  // namespace minibase

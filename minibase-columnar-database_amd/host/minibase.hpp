@@ -28,6 +28,7 @@
 
 #include "../../include/mbx.h"
 #include "../../include/mbx_db.h"
+#include "../../include/mbx_sort.h"
 
 // Everything lives in `minibase::` (the Java packages become nested
 // namespaces; `index` would otherwise collide with POSIX index(3)).
@@ -591,5 +592,23 @@ class ShardedColumnarIndexScan : public iterator::Iterator {
   bool rccl_ = false;
 };
 }  // namespace index
+
+namespace input {
+
+// R/input/ColumnarSort.java: the `sort` command's operator.  The reference
+// copies (sort columns, position) records into a heap file and merge-sorts its
+// pages through numBufForSort buffers (:229-353); here the same order -- the
+// comparator (:170-207), equal keys in the order the page passes leave them
+// (include/mbx_sort.h) -- comes from one GPU radix sort of the staged columns.
+// No run files are created and the DB file is not written.
+class ColumnarSort {
+ public:
+  // positions of every record of the column heap files (deleted rows included,
+  // as the reference scans them), in the result heap file's scan order
+  static std::vector<int64_t> sortedPositions(const columnar::Columnarfile& cf, const std::vector<int>& sortCols,
+                                              bool descending, int numBufForSort);
+};
+
+}  // namespace input
 
 }  // namespace minibase

@@ -104,13 +104,20 @@ EXPORTS = [
     "mbx_db_purge", "mbx_db_stage_range", "mbx_db_bitmap_stage_range",
     # include/mbx_join.h
     "mbx_join", "mbx_join_info", "mbx_join_fetch", "mbx_join_free", "mbx_gather",
+    # include/mbx_sort.h
+    "mbx_sort", "mbx_sort_info", "mbx_sort_fetch", "mbx_sort_free",
 ]
 JOIN_BMJ, JOIN_NLJ = 0, 1
+SORT_ASC, SORT_DSC = 0, 1
 
 
 class JoinTerm(ctypes.Structure):
     _fields_ = [("op", ctypes.c_int32), ("outer_col", ctypes.c_int32), ("inner_col", ctypes.c_int32),
                 ("pad_", ctypes.c_int32)]
+
+
+class SortKey(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 class JoinCnf(ctypes.Structure):
@@ -231,6 +238,10 @@ def lib():
         "mbx_join_fetch": ([V, V, I64, I64, V, V, V], ctypes.c_int),
         "mbx_join_free": ([V], ctypes.c_int),
         "mbx_gather": ([V, V, V, I64, P(I32), I32, P(V)], ctypes.c_int),
+        "mbx_sort": ([V, V, V, P(SortKey), I32, I32, I32, P(V)], ctypes.c_int),
+        "mbx_sort_info": ([V, P(I64), P(I32), P(I32)], ctypes.c_int),
+        "mbx_sort_fetch": ([V, V, I64, I64, V], ctypes.c_int),
+        "mbx_sort_free": ([V], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -425,6 +436,26 @@ class Context:
             return op_[:n.value], ip_[:n.value], ps[:n.value], p.value
         finally:
             lib().mbx_join_free(h)
+
+    def sort(self, table, keys, order=SORT_ASC, run_pages=0, sel=None, info=False):
+        """mbx_sort: global positions of the rows of `table` (of `sel`'s rows)
+        ordered by the 0-based columns `keys`; ties by position (run_pages 0)
+        or in the reference's order (run_pages = NUMBUF_SORT - 1).  info=True:
+        (positions, passes run, passes total)."""
+        karr = (SortKey * max(1, len(keys)))()
+        for k, col in enumerate(keys):
+            karr[k].col = col
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_sort(self.h, table.h, None if sel is None else sel.h, karr, len(keys), order, run_pages,
+                            ctypes.byref(h)))
+        try:
+            n, pr, pt = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+            _chk(lib().mbx_sort_info(h, ctypes.byref(n), ctypes.byref(pr), ctypes.byref(pt)))
+            pos = np.zeros(max(1, n.value), dtype=np.int64)
+            _chk(lib().mbx_sort_fetch(self.h, h, 0, n.value, pos.ctypes.data))
+            return (pos[:n.value], pr.value, pt.value) if info else pos[:n.value]
+        finally:
+            lib().mbx_sort_free(h)
 
     def gather(self, table, positions, proj):
         pos = np.ascontiguousarray(positions, dtype=np.int64)

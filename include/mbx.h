@@ -182,13 +182,48 @@ int mbx_table_info(const mbx_table *t, int64_t *nrows, int64_t *row_offset, int3
  * then gathers of grouped columns return the snapshot's values (and a HIP
  * graph captured before a drop must not be replayed after it). */
 int mbx_table_group(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t ncols);
+/* Byte-plane slices (no reference counterpart; a physical layout choice of
+ * the executor): a device-built, table-owned copy of the
+ * named int32 columns (cols, 0-based; another type: MBX_E_TYPE) as byte
+ * planes of the key (uint32)x ^ 0x80000000 -- plane p holds byte p (0 = most
+ * significant) of every row's key, contiguous.  Leading planes on which the
+ * column's smallest and largest key agree are not stored (values in
+ * [0, 2^20) keep 3 planes, [256, 511] keeps 1).  COUNT scans of plans bound
+ * to the slices (mbx_plan_compile) read planes top-down and only as deep as
+ * some row still needs: `c < 2^19` over [0, 2^20) reads 1 byte per row
+ * instead of 4.  Results are identical; BitSet, select and aggregate scans
+ * keep reading the columns.  Costs one read of the column, and stored-planes
+ * bytes x nrows of HBM, once per column.  A slice is a snapshot taken at
+ * this call: for a table over caller memory (mbx_table_wrap) whose columns
+ * the caller rewrites, drop the slices (ncols = 0, cols may be NULL) and
+ * slice again after the rewrite -- until then COUNT scans of bound plans
+ * return the snapshot's counts (and a HIP graph captured before a drop must
+ * not be replayed after it).  Naming a column that is already sliced
+ * rebuilds it.  A drop or rebuild unbinds every plan compiled before it:
+ * their COUNT scans read the live columns again (no allocation at launch). */
+int mbx_table_slice(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t ncols);
+/* *stored_planes = the planes column `col` keeps (1..4), 0: not sliced */
+int mbx_table_slice_info(const mbx_table *t, int32_t col, int32_t *stored_planes);
 
 /* ---- predicates: PredEval.Eval over one tuple (R/iterator/PredEval.java:25-183),
  * compiled once for one table.  Type rules follow the reference: the
  * comparison type is operand1's, both operands must carry it (else
  * MBX_E_TYPE); FldSpec offsets are checked (MBX_E_RANGE). ----------------- */
+/* Slices (tuning knob auto_slice, default 1): a plan whose every term is
+ * `int32 column OP int literal` (either operand order, 1..4 terms on <= 4
+ * columns, any CNF shape) has the missing slices of its columns built here
+ * (mbx_table_slice; never at launch, so never under a graph capture) and its
+ * COUNT scans (mbx_scan_count, _async, _frame_async) bound to them.  Such a
+ * plan is a snapshot plan: over mbx_table_wrap memory the caller rewrites,
+ * its COUNT keeps the values of this call until mbx_table_slice drops or
+ * rebuilds the slices, as for column groups.  If the slices cannot be
+ * allocated the plan scans the columns and no error is raised;
+ * auto_slice = 0 compiles every plan onto the columns. */
 int mbx_plan_compile(mbx_ctx *ctx, const mbx_table *t, const mbx_cnf *cnf, mbx_plan **out);
 int mbx_plan_free(mbx_plan *p);
+/* *sliced = 1 when COUNT launches of this plan currently take the sliced
+ * kernel (bound at compile, slices not dropped or rebuilt since), else 0 */
+int mbx_plan_sliced(mbx_ctx *ctx, const mbx_plan *p, int32_t *sliced);
 
 /* ---- ColumnarFileScan (R/iterator/ColumnarFileScan.java:156-188) --------- */
 /* COUNT of get_next() results: Query.executeFileScan's resultCount. */
@@ -438,7 +473,7 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * "scan_hoist", "scan_ri", "sink_lds", "ticket_groups", "fin_mode",
  * "join_plain", "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
- * "comm_same_stream", "scan_words_wt", and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
+ * "comm_same_stream", "scan_words_wt", "auto_slice" (mbx_plan_compile above), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,
  * 2 write-through, 3 nontemporal); "reset" restores the defaults. */
 int mbx_set_tuning(mbx_ctx *ctx, const char *knob, int64_t value);

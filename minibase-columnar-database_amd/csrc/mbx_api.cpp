@@ -105,6 +105,7 @@ static void tuning_defaults(MbxTuning& t) {
   t.select_flag_stride = (int32_t)env_knob("MBX_SELECT_FLAG_STRIDE", kFlagStride);
   t.scan_words_wt = (int32_t)env_knob("MBX_SCAN_WORDS_WT", 1);
   t.comm_same_stream = (int32_t)env_knob("MBX_COMM_SAME_STREAM", 1);
+  t.auto_slice = env_knob("MBX_AUTO_SLICE", 1) != 0;
   t.cnf_blocks = (int32_t)env_knob("MBX_CNF_BLOCKS", 0);
   t.cnf_flag_stride = env_knob("MBX_CNF_FLAG_STRIDE", 1) == kFlagStride ? kFlagStride : 1;
   t.cnf_lookback = (int32_t)env_knob("MBX_CNF_LOOKBACK", 0);
@@ -333,6 +334,7 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
   else if (!strcmp(knob, "select_flag_stride")) t.select_flag_stride = v == 1 ? 1 : kFlagStride;
   else if (!strcmp(knob, "scan_words_wt")) t.scan_words_wt = v != 0;
   else if (!strcmp(knob, "comm_same_stream")) t.comm_same_stream = v != 0;
+  else if (!strcmp(knob, "auto_slice")) t.auto_slice = v != 0;
   else return fail(MBX_E_INVALID, "mbx_set_tuning: unknown knob `%s`", knob);
   return MBX_OK;
 }
@@ -433,6 +435,7 @@ extern "C" int mbx_table_free(mbx_table* t) {
   for (auto& c : t->cols)
     if (c.owned) hipFree(c.dev);
   for (auto& g : t->groups) hipFree(g.dev);
+  for (auto& sl : t->slices) hipFree(sl.dev);
   if (t->owns_deleted) hipFree(t->deleted);
   delete t;
   return MBX_OK;
@@ -484,6 +487,86 @@ extern "C" int mbx_table_group(mbx_ctx* c, mbx_table* t, const int32_t* cols, in
     return fail(MBX_E_DEVICE, "table_group: %s", hipGetErrorString(e));
   }
   t->groups.push_back(g);
+  return MBX_OK;
+}
+
+// Byte-plane slices of one int32 column: the key range
+// on the device, then the planes below the range's constant prefix.  One read
+// of the column and a write of <= 4 bytes per row; synchronous.
+static int slice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
+  const int32_t* src = (const int32_t*)t->cols[(size_t)col].dev;
+  const int64_t tiles = (t->nrows + kSliceTileRows - 1) / kSliceTileRows;
+  const int64_t pstride = (tiles < 1 ? 1 : tiles) * kSliceTileRows;
+  uint32_t* dmm = nullptr;
+  if (hipMalloc(&dmm, 2 * sizeof(uint32_t)) != hipSuccess) return fail(MBX_E_NOMEM, "table_slice: scratch");
+  uint32_t mm[2] = {~0u, 0u};
+  hipError_t e = hipMemcpyAsync(dmm, mm, sizeof(mm), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_slice_minmax(src, t->nrows, dmm, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(mm, dmm, sizeof(mm), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  hipFree(dmm);
+  if (e != hipSuccess) return fail(MBX_E_DEVICE, "table_slice: %s", hipGetErrorString(e));
+  if (mm[0] > mm[1]) mm[0] = mm[1] = 0x80000000u;  // no rows
+  TSlice sl;
+  sl.kmin = mm[0];
+  sl.kmax = mm[1];
+  sl.first = 0;  // leading planes on which min and max agree; the last plane is always stored
+  while (sl.first < 3 && (mm[0] >> (24 - 8 * sl.first)) == (mm[1] >> (24 - 8 * sl.first))) sl.first++;
+  sl.stored = 4 - sl.first;
+  const size_t bytes = (size_t)sl.stored * (size_t)pstride;
+  if (hipMalloc(&sl.dev, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MBX_E_NOMEM, "table_slice: %zu bytes", bytes);
+  }
+  e = launch_slice_build(src, t->nrows, sl.first, pstride, sl.dev, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    hipFree(sl.dev);
+    return fail(MBX_E_DEVICE, "table_slice: %s", hipGetErrorString(e));
+  }
+  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
+  t->slices[(size_t)col] = sl;
+  return MBX_OK;
+}
+
+extern "C" int mbx_table_slice(mbx_ctx* c, mbx_table* t, const int32_t* cols, int32_t ncols) {
+  NOTNULL(c);
+  NOTNULL(t);
+  if (c->capturing) return fail(MBX_E_INVALID, "table_slice: inside a graph capture (it allocates)");
+  if (ncols < 0) return fail(MBX_E_INVALID, "table_slice: ncols = %d", ncols);
+  if (ncols > 0) NOTNULL(cols);
+  for (int32_t k = 0; k < ncols; k++) {
+    if (cols[k] < 0 || cols[k] >= (int32_t)t->cols.size())
+      return fail(MBX_E_RANGE, "table_slice: column %d outside 0..%zu", cols[k], t->cols.size() - 1);
+    if (t->cols[(size_t)cols[k]].attr_type != MBX_ATTR_INTEGER)
+      return fail(MBX_E_TYPE, "table_slice: column %d is not an int32 column", cols[k]);
+  }
+  int rc = set_device(c);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));  // no launch in flight still reads a slice
+  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
+  bool dropped = false;
+  for (size_t j = 0; j < t->slices.size(); j++) {
+    bool named = ncols == 0;  // ncols = 0: drop every slice
+    for (int32_t k = 0; k < ncols; k++) named = named || cols[k] == (int32_t)j;
+    if (named && t->slices[j].stored) {
+      hipFree(t->slices[j].dev);
+      t->slices[j] = TSlice();
+      dropped = true;
+    }
+  }
+  if (dropped) t->slice_gen++;  // plans bound to the dropped slices scan the columns from now on
+  for (int32_t k = 0; k < ncols; k++)
+    if (!t->slices[(size_t)cols[k]].stored && (rc = slice_build_col(c, t, cols[k]))) return rc;
+  return MBX_OK;
+}
+
+extern "C" int mbx_table_slice_info(const mbx_table* t, int32_t col, int32_t* stored_planes) {
+  NOTNULL(t);
+  NOTNULL(stored_planes);
+  if (col < 0 || col >= (int32_t)t->cols.size())
+    return fail(MBX_E_RANGE, "table_slice_info: column %d outside 0..%zu", col, t->cols.size() - 1);
+  *stored_planes = (size_t)col < t->slices.size() ? t->slices[(size_t)col].stored : 0;
   return MBX_OK;
 }
 
@@ -986,6 +1069,107 @@ static int plan_variant(mbx_plan* p, int32_t agg_col, PlanVariant** out) {
   return MBX_OK;
 }
 
+// Sliced COUNT scan eligibility: 1..4 terms `int32 column OP int literal`
+// (either operand order: the range form normalises both) over <= 4 columns,
+// any CNF shape.  Never-true int terms are dropped by compile_into; a plan
+// that keeps no term references no column and stays on the column scan.
+static bool slice_eligible(const mbx_plan* p) {
+  const KPlan& h = p->host;
+  if (!p->all_literal || h.has_real || p->ctx->tune.force_generic) return false;
+  if (h.nterms < 1 || h.nterms > kSliceMaxTerms) return false;
+  if (p->slot_col.empty() || p->slot_col.size() > (size_t)kSliceMaxCols) return false;
+  for (int32_t i = 0; i < h.nterms; i++)
+    if (h.terms[i].kind != kInt || h.terms[i].rhs >= 0) return false;
+  for (int32_t col : p->slot_col)
+    if (p->t->cols[(size_t)col].attr_type != MBX_ATTR_INTEGER) return false;
+  return true;
+}
+
+// One bound of a term against a column's slices: its state after the
+// constant prefix and the last plane that has to compare it.  Equal rows are
+// decided once the bound's remaining bytes are all 0x00 (lower) / 0xFF
+// (upper): equal then means the bound holds.
+static void slice_bound_of(uint32_t key, bool upper, const TSlice& sl, int32_t* state, int32_t* dlast) {
+  *dlast = -1;
+  if (sl.first > 0) {
+    const int sh = 32 - 8 * sl.first;
+    const uint32_t cp = sl.kmin >> sh, bp = key >> sh;
+    if (cp != bp) {
+      *state = (upper ? cp < bp : cp > bp) ? kSliceHolds : kSliceFails;
+      return;
+    }
+  }
+  for (int p = sl.first - 1; p <= 3; p++) {
+    const uint64_t rest = (uint64_t(1) << (24 - 8 * p)) - 1;  // the bytes below plane p
+    if ((key & rest) == (upper ? (uint32_t)rest : 0u)) {
+      if (p < sl.first) {
+        *state = kSliceHolds;
+        return;
+      }
+      *state = kSliceEqual;
+      *dlast = p;
+      return;
+    }
+  }
+}
+
+// Builds the missing slices of the plan's columns and binds the plan's COUNT
+// scans to them.  Any failure leaves the plan unbound (the column scan).
+static void bind_slices(mbx_ctx* c, mbx_plan* p) {
+  const mbx_table* t = p->t;
+  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
+  for (int32_t col : p->slot_col)
+    if (!t->slices[(size_t)col].stored) {
+      if (c->capturing || slice_build_col(c, t, col)) return;
+    }
+  const KPlan& h = p->host;
+  KSlicePlan sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.ncols = (int32_t)p->slot_col.size();
+  sp.nterms = h.nterms;
+  const int64_t tiles = (t->nrows + kSliceTileRows - 1) / kSliceTileRows;
+  sp.pstride = (tiles < 1 ? 1 : tiles) * kSliceTileRows;
+  for (int32_t s = 0; s < sp.ncols; s++) {
+    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)s]];
+    sp.planes[s] = sl.dev;
+    sp.first[s] = sl.first;
+  }
+  for (int32_t i = 0; i < h.nterms; i++) {
+    const KTerm& kt = h.terms[i];
+    KSliceTerm& st = sp.terms[i];
+    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
+    st.klo = (uint32_t)kt.rlo ^ 0x80000000u;
+    st.khi = st.klo + kt.rspan;  // int_range_of: lo <= hi as ints, no wrap
+    int32_t slo, shi, dlo, dhi;
+    slice_bound_of(st.klo, false, sl, &slo, &dlo);
+    slice_bound_of(st.khi, true, sl, &shi, &dhi);
+    st.meta = slice_term_meta(kt.lhs, kt.rneg, slo, shi, dlo, dhi);
+  }
+  // the required conjuncts: one term mask each; one without terms selects no row
+  for (uint32_t bit = 1; bit; bit <<= 1) {
+    if (!(h.all_conj & bit)) continue;
+    uint32_t m = 0;
+    for (int32_t i = 0; i < h.nterms; i++)
+      if (h.terms[i].conj_bit == bit) m |= 1u << i;
+    if (!m)
+      sp.never = 1;
+    else
+      sp.cmask[sp.nconj++] = m;
+  }
+  KSlicePlan* dev = nullptr;
+  if (hipMalloc(&dev, sizeof(KSlicePlan)) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  if (hipMemcpy(dev, &sp, sizeof(KSlicePlan), hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(dev);
+    return;
+  }
+  p->sliced = dev;
+  p->sliced_ncols = sp.ncols;
+  p->slice_gen = t->slice_gen;
+}
+
 extern "C" int mbx_plan_compile(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_plan** out) {
   NOTNULL(c);
   NOTNULL(t);
@@ -1002,6 +1186,7 @@ extern "C" int mbx_plan_compile(mbx_ctx* c, const mbx_table* t, const mbx_cnf* c
     mbx_plan_free(p);
     return rc;
   }
+  if (c->tune.auto_slice && slice_eligible(p)) bind_slices(c, p);  // unbound on failure: the column scan
   *out = p;
   return MBX_OK;
 }
@@ -1011,6 +1196,7 @@ extern "C" int mbx_plan_free(mbx_plan* p) {
   hipSetDevice(p->ctx->device);
   hipStreamSynchronize(p->ctx->stream);
   for (auto& v : p->variants) hipFree(v.dev);
+  hipFree(p->sliced);
   delete p;
   return MBX_OK;
 }
@@ -1031,6 +1217,40 @@ static int32_t ticket_groups_of(const mbx_ctx* c) {
   return g > kMaxTicketGroups ? kDefaultTicketGroups : g;
 }
 
+// COUNT launches of a plan take the sliced kernel while the table's slices are
+// the generation the plan was bound to (mbx_table_slice drops / rebuilds bump it)
+static bool plan_sliced_now(const mbx_plan* p) { return p->sliced && p->slice_gen == p->t->slice_gen; }
+
+// Segment size and grid of the plan's COUNT launch; true: the sliced kernel,
+// whose segments count 1024-row tiles.  It runs twice the column scan's blocks
+// (~2048, 8 waves per SIMD): a tile that needs a deeper plane waits for that
+// load with nothing else of its wave in flight, and the second set of waves
+// covers it -- 100 M rows, builder box: `c == 12345` 64.8 -> 51.6 us,
+// `c < 104858` 55.6 -> 44.8, C3 (one plane per column) 44.9 -> 41.0.  At least
+// 16 tiles per block (4 per wave: one full group of tiles in flight); the
+// tiles_per_block knob keeps its meaning in rows (4 x 256 = one sliced tile).
+static bool count_geometry(const mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int64_t* tpb, int64_t* nb) {
+  *tpb = scan_tiles_per_block(c, p->t->nrows, v);
+  if (plan_sliced_now(p)) {
+    if (c->tune.tiles_per_block > 0)
+      *tpb = (*tpb + 3) / 4;
+    else
+      *tpb = std::max<int64_t>((*tpb + 7) / 8, 16);
+    *nb = sliced_grid_blocks(p->t->nrows, *tpb);
+    return true;
+  }
+  *nb = grid_blocks(p->t->nrows, *tpb);
+  return false;
+}
+
+extern "C" int mbx_plan_sliced(mbx_ctx* c, const mbx_plan* p, int32_t* sliced) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(sliced);
+  *sliced = plan_sliced_now(p) ? 1 : 0;
+  return MBX_OK;
+}
+
 // k_scan_select's extra arguments (a BitSet scan that also writes the positions)
 struct FusedSelect {
   int64_t* ids;
@@ -1040,7 +1260,9 @@ struct FusedSelect {
 static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode, uint64_t* out_words,
                         Partial* parts, int64_t tpb, int64_t* count_out, AggOut* agg_out, int32_t* nan_out,
                         int64_t* seg_counts = nullptr, const FusedSelect* fused = nullptr,
-                        bool need_count = true, bool frame = false) {
+                        bool need_count = true, bool frame = false, bool sliced = false) {
+  // sliced: tpb counts sliced tiles and the launch is k_scan_sliced over the plan's slices
+  const int64_t nb = sliced ? sliced_grid_blocks(p->t->nrows, tpb) : grid_blocks(p->t->nrows, tpb);
   ScanLaunch L;
   L.plan = v.dev;
   L.nrows = p->t->nrows;
@@ -1092,8 +1314,8 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
   // slot -- plain partial stores and a separate fold launch instead (C5 125 M
   // rows: scan 472.7 -> 458.4 us + a 6 us fold, query 481 -> 471 us,
   // profiles/r03/c5fin)
-  if (tu.fin_mode < 0 && mode == kModeAgg && grid_blocks(L.nrows, tpb) > kResidentBlocks) L.fin_mode = kFinSeparate;
-  if (L.fin_mode == kFinPackedCount && !packed_count_fits(L.nrows, grid_blocks(L.nrows, tpb), L.ticket_groups))
+  if (tu.fin_mode < 0 && mode == kModeAgg && nb > kResidentBlocks) L.fin_mode = kFinSeparate;
+  if (L.fin_mode == kFinPackedCount && !packed_count_fits(L.nrows, nb, L.ticket_groups))
     L.fin_mode = kFinWriteThrough;
   if ((L.fin_mode == kFinPackedCount || L.fin_mode == kFinSegOnly) && mode == kModeAgg) L.fin_mode = kFinWriteThrough;
   if (L.fin_mode > kFinSegOnly) L.fin_mode = kFinWriteThrough;
@@ -1120,9 +1342,14 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                               c->tune.select_dbg >> 4, c->tune.scan_select_waves, c->tune.select_flag_stride));
     return MBX_OK;
   }
-  HIPCHK(launch_scan(L, c->stream));
+  if (sliced) {
+    L.sl = p->sliced;
+    HIPCHK(launch_scan_sliced(L, p->sliced_ncols, c->stream));
+  } else {
+    HIPCHK(launch_scan(L, c->stream));
+  }
   if (L.fin_mode == kFinSeparate)
-    HIPCHK(launch_finalize(parts, grid_blocks(L.nrows, tpb), L.agg_kind, agg_out, count_out, nan_out, c->stream));
+    HIPCHK(launch_finalize(parts, nb, L.agg_kind, agg_out, count_out, nan_out, c->stream));
   return MBX_OK;
 }
 
@@ -1130,10 +1357,11 @@ static int scan_to_count(mbx_ctx* c, mbx_plan* p, int64_t* dev_count, int32_t* d
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  const int64_t tpb = scan_tiles_per_block(c, p->t->nrows, *v);
-  const int64_t nb = grid_blocks(p->t->nrows, tpb);
+  int64_t tpb, nb;
+  const bool sliced = count_geometry(c, p, *v, &tpb, &nb);
   if ((rc = ensure_partials(c, nb))) return rc;
-  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_count, nullptr, dev_nan);
+  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_count, nullptr, dev_nan, nullptr, nullptr,
+                      true, false, sliced);
 }
 
 // NaN words: the *_async entry points report through dnan[0..1] ([1] sticky
@@ -1204,14 +1432,14 @@ extern "C" int mbx_scan_count_frame_async(mbx_ctx* c, const mbx_plan* pc, int64_
   if (rc) return rc;
   PlanVariant* v = nullptr;
   if ((rc = plan_variant(p, -1, &v))) return rc;
-  const int64_t tpb = scan_tiles_per_block(c, p->t->nrows, *v);
-  const int64_t nb = grid_blocks(p->t->nrows, tpb);
+  int64_t tpb, nb;
+  const bool sliced = count_geometry(c, p, *v, &tpb, &nb);
   if ((nb + kFrameSlots - 1) / kFrameSlots > kFrameMaxArrivalsPerSlot || p->t->nrows >= (int64_t(1) << 36))
     return fail(MBX_E_INVALID, "scan_count_frame: %lld rows in %lld blocks do not fit a count frame",
                 (long long)p->t->nrows, (long long)nb);
   if ((rc = ensure_partials(c, nb))) return rc;
   return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_frame, nullptr, c->dnan, nullptr, nullptr,
-                      true, true);
+                      true, true, sliced);
 }
 
 extern "C" int mbx_count_frame_fits(int64_t nblocks, int32_t nranks) {
@@ -1244,7 +1472,8 @@ extern "C" int mbx_scan_blocks(mbx_ctx* c, const mbx_plan* pc, int64_t* blocks) 
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  *blocks = grid_blocks(p->t->nrows, scan_tiles_per_block(c, p->t->nrows, *v));
+  int64_t tpb;
+  count_geometry(c, p, *v, &tpb, blocks);
   return MBX_OK;
 }
 

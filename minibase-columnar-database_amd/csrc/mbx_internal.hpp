@@ -156,6 +156,47 @@ struct ScanLaunch {
   int32_t words_wt;           // BitSet words stored write-through (sc1) instead of plain
   int32_t int_range;          // branch-free range-test term body: 1 every term an int literal
                               // compare, 2 literal compares of any type (int / float / char(16))
+  const struct KSlicePlan* sl = nullptr;  // sliced COUNT scan (k_scan_sliced): device; tiles_per_block
+                                          // then counts sliced tiles (kSliceTileRows rows)
+};
+
+// ---- byte-plane slices of int32 columns (mbx_table_slice)
+// Key of a value x: k = (uint32)x ^ 0x80000000 (unsigned byte order == signed
+// int order).  Plane p (0 = most significant) holds byte p of every row's key;
+// leading planes on which the column's key min and max agree are a constant
+// prefix and are not stored.  A sliced tile is 1024 rows per wave: one 16-byte
+// load per lane per plane, 16 consecutive rows per lane.
+constexpr int kSliceTileRows = 1024;
+constexpr int kSliceMaxCols = 4;
+constexpr int kSliceMaxTerms = 4;
+
+// One term `lo <= k <= hi` (negated when neg) of a sliced COUNT plan.  A bound
+// is compared plane by plane while rows are still equal to it; the host
+// resolved it against the column's constant prefix (state) and found the plane
+// after which equal rows are decided (a lower bound whose remaining bytes are
+// all 0x00, an upper bound whose remaining bytes are all 0xFF: equal holds).
+enum SliceState : int32_t { kSliceEqual = 0, kSliceHolds = 1, kSliceFails = 2 };
+struct KSliceTerm {
+  uint32_t klo, khi;   // key bounds
+  uint32_t meta;       // slice_term_meta: the rest, packed (the kernel keeps a term in 3 scalar registers)
+  uint32_t pad_;
+};
+// col: column slot; neg; slo / shi: SliceState of each bound after the constant
+// prefix; dlo / dhi: the last plane (0..3) that compares the bound, -1: none
+inline uint32_t slice_term_meta(int32_t col, int32_t neg, int32_t slo, int32_t shi, int32_t dlo, int32_t dhi) {
+  return (uint32_t)col | ((uint32_t)(neg != 0) << 2) | ((uint32_t)slo << 3) | ((uint32_t)shi << 5) |
+         ((uint32_t)(dlo + 1) << 7) | ((uint32_t)(dhi + 1) << 10);
+}
+
+struct KSlicePlan {
+  int32_t ncols, nterms;
+  int32_t nconj;       // required conjuncts that have terms
+  int32_t never;       // a required conjunct without terms: no row is selected
+  uint32_t cmask[kSliceMaxTerms];        // terms (bit ti) of conjunct q
+  const uint8_t* planes[kSliceMaxCols];  // first stored plane of column slot c
+  int32_t first[kSliceMaxCols];          // its plane number (4 - stored planes)
+  int64_t pstride;                       // bytes between planes (rows padded to a whole tile)
+  KSliceTerm terms[kSliceMaxTerms];
 };
 
 // dynamic LDS per block for the staged BitSet (4 blocks per CU: <= 128 KB of
@@ -330,6 +371,15 @@ int64_t grid_blocks(int64_t nrows, int64_t tiles_per_block);
 int64_t choose_tiles_per_block(int64_t nrows);
 
 hipError_t launch_scan(const ScanLaunch& L, hipStream_t s);
+// sliced COUNT scan: L.sl set, L.tiles_per_block in sliced tiles, ncols = the plan's column slots
+int64_t sliced_grid_blocks(int64_t nrows, int64_t tiles_per_block);
+hipError_t launch_scan_sliced(const ScanLaunch& L, int32_t ncols, hipStream_t s);
+// key min / max of an int32 column into mm[0..1] (mm preset to ~0u, 0u)
+hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, hipStream_t s);
+// planes first..3 of the column's keys into out (plane p at out + (p - first) * pstride;
+// pstride = rows padded to a whole sliced tile, the padding written as 0)
+hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, int64_t pstride, uint8_t* out,
+                              hipStream_t s);
 hipError_t launch_finalize(const Partial* partials, int64_t nblocks, int32_t agg_kind, AggOut* out,
                            int64_t* count_out, int32_t* nan_flag, hipStream_t s);
 // one launch: words of the CNF (never stored) -> positions (ids may be null)

@@ -69,6 +69,8 @@ struct MbxTuning {
   int32_t select_flag_stride = 16; // MBX_SELECT_FLAG_STRIDE: 16 = k_scan_select's polled flags one per line, or 1
   int32_t scan_words_wt = 1;      // MBX_SCAN_WORDS_WT: BitSet scan words stored write-through
   int32_t comm_same_stream = 1;   // MBX_COMM_SAME_STREAM: collectives on the context stream (0: the exchange stream)
+  int32_t auto_slice = 1;         // MBX_AUTO_SLICE: mbx_plan_compile builds byte-plane slices of the int32 columns of a
+                                  // slice-eligible plan and binds its COUNT scans to them (0: plans read the columns)
   int32_t select_dbg = 0;         // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
                                   // instead of the chained look-back, 512 write-through flip; -DMBX_DIAG
                                   // builds only: k_select_ids bit 0 no prefix / bit 1 no emission, the
@@ -109,12 +111,26 @@ struct TGroup {
   uint32_t* dev = nullptr;
 };
 
+// byte-plane slices of one int32 column (mbx_table_slice): planes first..3 of
+// its keys, plane p at dev + (p - first) * pstride; stored == 0: none
+struct TSlice {
+  int32_t stored = 0;   // planes kept (4 - first): the key's constant prefix is not stored
+  int32_t first = 4;
+  uint32_t kmin = 0, kmax = 0;  // key range of the column when it was sliced
+  uint8_t* dev = nullptr;
+};
+
 struct mbx_table {
   mbx_ctx* ctx = nullptr;
   int64_t nrows = 0;
   int64_t row_offset = 0;
   std::vector<TCol> cols;
   std::vector<TGroup> groups;  // owned
+  // derived layout built on demand by mbx_plan_compile (which takes a const
+  // table): one entry per column, owned.  slice_gen counts drops / rebuilds; a
+  // plan bound to an older generation scans the columns.
+  mutable std::vector<TSlice> slices;
+  mutable uint64_t slice_gen = 0;
   uint64_t* deleted = nullptr;
   bool owns_deleted = false;
   bool aligned16 = true;
@@ -136,6 +152,11 @@ struct mbx_plan {
   bool all_literal = true;        // every term is `column OP literal`
   bool str_lit_fits16 = true;     // every string literal is <= 16 bytes
   std::deque<PlanVariant> variants;
+  // sliced COUNT scan (k_scan_sliced): the device plan over the table's slices
+  // of generation slice_gen; null: COUNT scans read the columns
+  mbx::KSlicePlan* sliced = nullptr;
+  int32_t sliced_ncols = 0;
+  uint64_t slice_gen = 0;
 };
 
 struct mbx_bitmap {

@@ -80,7 +80,7 @@ def java_mutf8(s):
 
 EXPORTS = [
     "mbx_abi_version", "mbx_last_error", "mbx_device_count", "mbx_init", "mbx_free", "mbx_sync", "mbx_stream",
-    "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_plan_compile", "mbx_plan_free",
+    "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_table_slice", "mbx_table_slice_info", "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced",
     "mbx_scan_count", "mbx_scan_count_async", "mbx_scan_count_frame_async", "mbx_count_frame_decode",
     "mbx_count_frame_fits",
     "mbx_scan_blocks", "mbx_scan_bitmap", "mbx_scan_bitmap_async", "mbx_scan_select",
@@ -150,6 +150,9 @@ def lib():
         "mbx_table_free": ([V], ctypes.c_int),
         "mbx_table_info": ([V, P(I64), P(I64), P(I32)], ctypes.c_int),
         "mbx_table_group": ([V, V, P(I32), I32], ctypes.c_int),
+        "mbx_table_slice": ([V, V, P(I32), I32], ctypes.c_int),
+        "mbx_table_slice_info": ([V, I32, P(I32)], ctypes.c_int),
+        "mbx_plan_sliced": ([V, V, P(I32)], ctypes.c_int),
         "mbx_plan_compile": ([V, V, P(Cnf), P(V)], ctypes.c_int),
         "mbx_plan_free": ([V], ctypes.c_int),
         "mbx_scan_count": ([V, V, P(I64)], ctypes.c_int),
@@ -408,6 +411,26 @@ class Context:
         columns)."""
         arr = (ctypes.c_int32 * len(cols))(*cols) if cols else None
         _chk(lib().mbx_table_group(self.h, table.h, arr, len(cols)))
+
+    def slice(self, table, cols):
+        """mbx_table_slice: byte-plane slices of the named int32 columns, which
+        COUNT scans of plans compiled afterwards read instead of the columns
+        (same counts, fewer bytes); naming a sliced column rebuilds it, cols = []
+        drops every slice (a snapshot: rebuild after rewriting wrapped columns)."""
+        arr = (ctypes.c_int32 * len(cols))(*cols) if cols else None
+        _chk(lib().mbx_table_slice(self.h, table.h, arr, len(cols)))
+
+    def slice_info(self, table, col):
+        """mbx_table_slice_info: the byte planes column `col` keeps (0: not sliced)."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_table_slice_info(table.h, col, ctypes.byref(n)))
+        return n.value
+
+    def plan_sliced(self, plan):
+        """mbx_plan_sliced: True while the plan's COUNT launches take the sliced kernel."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_plan_sliced(self.h, plan.h, ctypes.byref(n)))
+        return bool(n.value)
 
     def join(self, outer, outer_sel, inner, inner_sel, cnf, order, outer_block=0):
         """mbx_join: cnf = [[(op, outer_col, inner_col), ...], ...] (0-based

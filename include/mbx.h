@@ -471,7 +471,8 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * reads no environment (a -DMBX_DIAG build, tools/build_diag.sh, also takes
  * MBX_<KNOB> environment values at mbx_init).  knob: "tiles_per_block", "force_generic",
  * "scan_hoist", "scan_ri", "sink_lds", "ticket_groups", "fin_mode",
- * "join_plain", "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
+ * "join_plain", "join_chunk_words" (pair-matrix words per chunk of mbx_join, 1 .. 2^24; anything else: 2^24),
+ * "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
  * "comm_same_stream", "scan_words_wt", "auto_slice" (mbx_plan_compile above), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,

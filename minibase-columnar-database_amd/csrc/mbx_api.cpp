@@ -95,6 +95,8 @@ static void tuning_defaults(MbxTuning& t) {
   t.ticket_groups = (int32_t)env_knob("MBX_TICKET_GROUPS", -1);
   t.fin_mode = (int32_t)env_knob("MBX_FIN_MODE", -1);
   t.join_plain = (int32_t)env_knob("MBX_JOIN_PLAIN", 0);
+  t.join_chunk_words = env_knob("MBX_JOIN_CHUNK_WORDS", kJoinChunkWords);
+  if (t.join_chunk_words < 1 || t.join_chunk_words > kJoinChunkWords) t.join_chunk_words = kJoinChunkWords;
   t.distinct_lds_probes = (int32_t)env_knob("MBX_DISTINCT_LDS_PROBES", -1);
   t.select_dbg = (int32_t)env_knob("MBX_SELECT_DBG", 0);
   t.gather_fused = (int32_t)env_knob("MBX_GATHER_FUSED", 1);
@@ -313,6 +315,9 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
     t.fin_mode = v;
   }
   else if (!strcmp(knob, "join_plain")) t.join_plain = v;
+  // never above the default: the join's scratch bound does not grow
+  else if (!strcmp(knob, "join_chunk_words"))
+    t.join_chunk_words = value >= 1 && value <= kJoinChunkWords ? value : kJoinChunkWords;
   else if (!strcmp(knob, "distinct_lds_probes")) t.distinct_lds_probes = v;
   else if (!strcmp(knob, "select_dbg")) {
     // k_select_ids takes bits 0-1, the one-launch selections bits 4-6: A/B

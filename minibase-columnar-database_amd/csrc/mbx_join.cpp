@@ -177,7 +177,8 @@ extern "C" int mbx_join(mbx_ctx* c, const mbx_table* outer, const mbx_bitmap* ou
   }
   A.words_per_row = wpr;
   // the pair matrix in chunks of rows: <= 2^24 words (128 MiB) of scratch
-  const int64_t chunk_rows = wpr > 0 ? std::max<int64_t>(1, ((int64_t)1 << 24) / wpr) : 1;
+  // (the join_chunk_words knob only lowers it: tests place the chunk boundary)
+  const int64_t chunk_rows = wpr > 0 ? std::max<int64_t>(1, c->tune.join_chunk_words / wpr) : 1;
   mbx_bitmap* m = nullptr;
   int64_t* ids = nullptr;
   int64_t ids_cap = 0;

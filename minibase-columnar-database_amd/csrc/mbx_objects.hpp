@@ -44,6 +44,7 @@ using mbx::Partial;
 // The knobs' defaults are the production forms.  Names in comments are the
 // environment variables a -DMBX_DIAG build reads at mbx_init (the default
 // library reads none: mbx_set_tuning only).
+constexpr int64_t kJoinChunkWords = (int64_t)1 << 24;  // mbx_join: <= 128 MiB of pair-matrix scratch
 struct MbxTuning {
   int64_t tiles_per_block = -1;   // MBX_TILES_PER_BLOCK: segment size of every scan / BitSet
   int32_t force_generic = 0;      // MBX_FORCE_GENERIC: plans compiled after this use k_scan_generic
@@ -55,6 +56,7 @@ struct MbxTuning {
   int32_t ticket_groups = -1;     // MBX_TICKET_GROUPS
   int32_t fin_mode = -1;          // MBX_FIN_MODE (FinMode)
   int32_t join_plain = 0;         // MBX_JOIN_PLAIN: k_join_matrix instead of the fast form
+  int64_t join_chunk_words = kJoinChunkWords;   // MBX_JOIN_CHUNK_WORDS: pair-matrix scratch words per chunk (1 .. 2^24)
   int32_t distinct_lds_probes = -1;  // MBX_DISTINCT_LDS_PROBES
   int32_t gather_fused = 1;       // MBX_GATHER_FUSED: 0 = compaction, then k_gather (two launches)
   int32_t gather_pair = 1;        // MBX_GATHER_PAIR: 0 = two 4-byte loads per grouped pair row instead of one 8-byte

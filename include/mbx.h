@@ -204,6 +204,29 @@ int mbx_table_group(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t nco
 int mbx_table_slice(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t ncols);
 /* *stored_planes = the planes column `col` keeps (1..4), 0: not sliced */
 int mbx_table_slice_info(const mbx_table *t, int32_t col, int32_t *stored_planes);
+/* Bit planes (BitWeaving/V): a sliced column may also
+ * own up to 8 bit planes, one bit per row each, of the highest bits on which
+ * its keys vary -- bit h downwards, h the highest bit set in kmin ^ kmax of
+ * the slice's key range (a range of < 256 keys that crosses a power of two,
+ * such as [-5, 4], is taken relative to kmin first, so its 10 values keep 4
+ * planes).  They are built by mbx_plan_compile, the first time a plan that can
+ * be decided from them reads the column (see there), live and die with the
+ * column's slice, and follow the same snapshot rule.
+ * *bits = the bit planes column `col` keeps (1..8), 0: none */
+int mbx_table_bitslice_info(const mbx_table *t, int32_t col, int32_t *bits);
+/* The rule, as pure host functions (no device needed).  mbx_bitslice_range:
+ * for a column whose keys span [kmin, kmax], *base = what is subtracted from a
+ * key before its bits are taken (0, or kmin for the narrow crossing range
+ * above), *high_bit = h (-1: a constant column), *bits = min(8, h + 1).
+ * mbx_bitslice_bound: the bound `key' >= key` (upper != 0: `key' <= key`) on
+ * such a column -- *state 1: every row holds it, 2: no row does (*depth = 0),
+ * 0: decided by comparing *depth bits from h downwards, rows still equal to
+ * the bound after them hold it (a lower bound's remaining bits are all 0, an
+ * upper bound's all 1).  A plan takes the bit planes when every bound of every
+ * term has *depth <= *bits on its column. */
+int mbx_bitslice_range(uint32_t kmin, uint32_t kmax, uint32_t *base, int32_t *high_bit, int32_t *bits);
+int mbx_bitslice_bound(uint32_t kmin, uint32_t kmax, uint32_t key, int32_t upper, int32_t *state,
+                       int32_t *depth);
 
 /* ---- predicates: PredEval.Eval over one tuple (R/iterator/PredEval.java:25-183),
  * compiled once for one table.  Type rules follow the reference: the
@@ -218,12 +241,24 @@ int mbx_table_slice_info(const mbx_table *t, int32_t col, int32_t *stored_planes
  * its COUNT keeps the values of this call until mbx_table_slice drops or
  * rebuilds the slices, as for column groups.  If the slices cannot be
  * allocated the plan scans the columns and no error is raised;
- * auto_slice = 0 compiles every plan onto the columns. */
+ * auto_slice = 0 compiles every plan onto the columns.
+ * Bit planes (tuning knob auto_bitslice, default 1): when every bound of such
+ * a plan is decided within the bit planes of its column (mbx_bitslice_bound:
+ * a column of few distinct keys, or a round literal such as `c < 2^19` over
+ * [0, 2^20), which reads 1 bit per row), the bit planes the plan reads are
+ * built here if they do not exist yet -- adding them to a slice unbinds no
+ * plan -- and its COUNT scans are bound to them instead of the byte planes.
+ * Other plans, plans compiled under a capture while planes are missing, and
+ * plans whose bit planes cannot be allocated take the byte planes;
+ * auto_bitslice = 0 binds every plan as if there were no bit planes. */
 int mbx_plan_compile(mbx_ctx *ctx, const mbx_table *t, const mbx_cnf *cnf, mbx_plan **out);
 int mbx_plan_free(mbx_plan *p);
 /* *sliced = 1 when COUNT launches of this plan currently take the sliced
  * kernel (bound at compile, slices not dropped or rebuilt since), else 0 */
 int mbx_plan_sliced(mbx_ctx *ctx, const mbx_plan *p, int32_t *sliced);
+/* *form = what COUNT launches of this plan currently read: 0 the columns,
+ * 1 byte planes, 2 bit planes (mbx_plan_sliced reports 1 for both 1 and 2) */
+int mbx_plan_slice_form(mbx_ctx *ctx, const mbx_plan *p, int32_t *form);
 
 /* ---- ColumnarFileScan (R/iterator/ColumnarFileScan.java:156-188) --------- */
 /* COUNT of get_next() results: Query.executeFileScan's resultCount. */
@@ -474,7 +509,7 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * "join_plain", "join_chunk_words" (pair-matrix words per chunk of mbx_join, 1 .. 2^24; anything else: 2^24),
  * "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
- * "comm_same_stream", "scan_words_wt", "auto_slice" (mbx_plan_compile above), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
+ * "comm_same_stream", "scan_words_wt", "auto_slice", "auto_bitslice" (mbx_plan_compile above), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,
  * 2 write-through, 3 nontemporal); "reset" restores the defaults. */
 int mbx_set_tuning(mbx_ctx *ctx, const char *knob, int64_t value);

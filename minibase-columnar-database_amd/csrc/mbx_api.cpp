@@ -108,6 +108,7 @@ static void tuning_defaults(MbxTuning& t) {
   t.scan_words_wt = (int32_t)env_knob("MBX_SCAN_WORDS_WT", 1);
   t.comm_same_stream = (int32_t)env_knob("MBX_COMM_SAME_STREAM", 1);
   t.auto_slice = env_knob("MBX_AUTO_SLICE", 1) != 0;
+  t.auto_bitslice = env_knob("MBX_AUTO_BITSLICE", 1) != 0;
   t.cnf_blocks = (int32_t)env_knob("MBX_CNF_BLOCKS", 0);
   t.cnf_flag_stride = env_knob("MBX_CNF_FLAG_STRIDE", 1) == kFlagStride ? kFlagStride : 1;
   t.cnf_lookback = (int32_t)env_knob("MBX_CNF_LOOKBACK", 0);
@@ -340,6 +341,7 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
   else if (!strcmp(knob, "scan_words_wt")) t.scan_words_wt = v != 0;
   else if (!strcmp(knob, "comm_same_stream")) t.comm_same_stream = v != 0;
   else if (!strcmp(knob, "auto_slice")) t.auto_slice = v != 0;
+  else if (!strcmp(knob, "auto_bitslice")) t.auto_bitslice = v != 0;
   else return fail(MBX_E_INVALID, "mbx_set_tuning: unknown knob `%s`", knob);
   return MBX_OK;
 }
@@ -440,7 +442,10 @@ extern "C" int mbx_table_free(mbx_table* t) {
   for (auto& c : t->cols)
     if (c.owned) hipFree(c.dev);
   for (auto& g : t->groups) hipFree(g.dev);
-  for (auto& sl : t->slices) hipFree(sl.dev);
+  for (auto& sl : t->slices) {
+    hipFree(sl.dev);
+    hipFree(sl.bdev);
+  }
   if (t->owns_deleted) hipFree(t->deleted);
   delete t;
   return MBX_OK;
@@ -534,6 +539,70 @@ static int slice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
   return MBX_OK;
 }
 
+// dwords between the bit planes of a table's columns: the rows padded to a whole bit tile
+static int64_t bit_pstride(int64_t nrows) {
+  const int64_t tiles = (nrows + kBitTileRows - 1) / kBitTileRows;
+  return (tiles < 1 ? 1 : tiles) * (kBitTileRows / 32);
+}
+
+// Bit planes of a sliced column, over the slice's key range: one more read of
+// the column and a write of <= 1 byte per row; synchronous.  Adds to the
+// slice and drops nothing, so slice_gen stays.
+static int bitslice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
+  TSlice& sl = t->slices[(size_t)col];
+  const mbx::BitRange br = mbx::bit_range_of(sl.kmin, sl.kmax);
+  if (br.w == 0) {  // a constant column: every bound is decided on the host
+    sl.bit_w = 0;
+    return MBX_OK;
+  }
+  const int64_t pstride = bit_pstride(t->nrows);
+  const size_t bytes = (size_t)br.w * (size_t)pstride * sizeof(uint32_t);
+  uint32_t* dev = nullptr;
+  if (hipMalloc(&dev, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MBX_E_NOMEM, "table bit planes: %zu bytes", bytes);
+  }
+  hipError_t e = launch_bitslice_build((const int32_t*)t->cols[(size_t)col].dev, t->nrows, br.base, br.h, br.w,
+                                       pstride, dev, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    hipFree(dev);
+    return fail(MBX_E_DEVICE, "table bit planes: %s", hipGetErrorString(e));
+  }
+  sl.bdev = dev;
+  sl.bit_w = br.w;
+  return MBX_OK;
+}
+
+extern "C" int mbx_table_bitslice_info(const mbx_table* t, int32_t col, int32_t* bits) {
+  NOTNULL(t);
+  NOTNULL(bits);
+  if (col < 0 || col >= (int32_t)t->cols.size())
+    return fail(MBX_E_RANGE, "table_bitslice_info: column %d outside 0..%zu", col, t->cols.size() - 1);
+  const int32_t w = (size_t)col < t->slices.size() ? t->slices[(size_t)col].bit_w : 0;
+  *bits = w > 0 ? w : 0;
+  return MBX_OK;
+}
+
+extern "C" int mbx_bitslice_range(uint32_t kmin, uint32_t kmax, uint32_t* base, int32_t* high_bit, int32_t* bits) {
+  if (kmin > kmax) return fail(MBX_E_INVALID, "bitslice_range: kmin %u > kmax %u", kmin, kmax);
+  const mbx::BitRange br = mbx::bit_range_of(kmin, kmax);
+  if (base) *base = br.base;
+  if (high_bit) *high_bit = br.h;
+  if (bits) *bits = br.w;
+  return MBX_OK;
+}
+
+extern "C" int mbx_bitslice_bound(uint32_t kmin, uint32_t kmax, uint32_t key, int32_t upper, int32_t* state,
+                                  int32_t* depth) {
+  NOTNULL(state);
+  NOTNULL(depth);
+  if (kmin > kmax) return fail(MBX_E_INVALID, "bitslice_bound: kmin %u > kmax %u", kmin, kmax);
+  uint32_t bits;
+  mbx::bit_bound_of(kmin, kmax, key, upper != 0, state, depth, &bits);
+  return MBX_OK;
+}
+
 extern "C" int mbx_table_slice(mbx_ctx* c, mbx_table* t, const int32_t* cols, int32_t ncols) {
   NOTNULL(c);
   NOTNULL(t);
@@ -556,6 +625,7 @@ extern "C" int mbx_table_slice(mbx_ctx* c, mbx_table* t, const int32_t* cols, in
     for (int32_t k = 0; k < ncols; k++) named = named || cols[k] == (int32_t)j;
     if (named && t->slices[j].stored) {
       hipFree(t->slices[j].dev);
+      hipFree(t->slices[j].bdev);
       t->slices[j] = TSlice();
       dropped = true;
     }
@@ -1118,6 +1188,70 @@ static void slice_bound_of(uint32_t key, bool upper, const TSlice& sl, int32_t* 
   }
 }
 
+// The required conjuncts of a plan as term masks (KSlicePlan / KBitPlan): one
+// without terms selects no row
+static void slice_conjuncts(const KPlan& h, uint32_t (&cmask)[kSliceMaxTerms], int32_t* nconj, int32_t* never) {
+  for (uint32_t bit = 1; bit; bit <<= 1) {
+    if (!(h.all_conj & bit)) continue;
+    uint32_t m = 0;
+    for (int32_t i = 0; i < h.nterms; i++)
+      if (h.terms[i].conj_bit == bit) m |= 1u << i;
+    if (!m)
+      *never = 1;
+    else
+      cmask[(*nconj)++] = m;
+  }
+}
+
+// Binds a slice-eligible plan whose columns are sliced to their bit planes
+// when every bound of every term is decided within the planes its column
+// keeps (bit_bound_of: depth <= W), building the planes it reads that do not
+// exist yet.  false: the plan takes the byte planes (not bit-decidable, under
+// a capture with planes missing, or no memory for planes / plan).
+static bool bind_bits(mbx_ctx* c, mbx_plan* p) {
+  const mbx_table* t = p->t;
+  const KPlan& h = p->host;
+  KBitPlan bp;
+  memset(&bp, 0, sizeof(bp));
+  bp.nterms = h.nterms;
+  bp.pstride = bit_pstride(t->nrows);
+  int32_t depth[kSliceMaxTerms] = {0, 0, 0, 0}, planes = 0;
+  for (int32_t i = 0; i < h.nterms; i++) {
+    const KTerm& kt = h.terms[i];
+    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
+    const uint32_t klo = (uint32_t)kt.rlo ^ 0x80000000u, khi = klo + kt.rspan;  // as bind_slices
+    const int32_t w = mbx::bit_range_of(sl.kmin, sl.kmax).w;
+    int32_t slo, shi, dlo, dhi;
+    KBitTerm& bt = bp.terms[i];
+    mbx::bit_bound_of(sl.kmin, sl.kmax, klo, false, &slo, &dlo, &bt.lo);
+    mbx::bit_bound_of(sl.kmin, sl.kmax, khi, true, &shi, &dhi, &bt.hi);
+    if (dlo > w || dhi > w) return false;
+    bt.meta = bit_term_meta(kt.rneg, slo, shi, dlo, dhi);
+    depth[i] = std::max(dlo, dhi);
+    planes += depth[i];
+  }
+  for (int32_t i = 0; i < h.nterms; i++) {
+    if (depth[i] == 0) continue;  // no plane of its column is read for this term
+    const int32_t col = p->slot_col[(size_t)h.terms[i].lhs];
+    if (t->slices[(size_t)col].bit_w < 0 && (c->capturing || bitslice_build_col(c, t, col))) return false;
+    bp.terms[i].planes = t->slices[(size_t)col].bdev;
+  }
+  slice_conjuncts(h, bp.cmask, &bp.nconj, &bp.never);
+  KBitPlan* dev = nullptr;
+  if (hipMalloc(&dev, sizeof(KBitPlan)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (hipMemcpy(dev, &bp, sizeof(KBitPlan), hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(dev);
+    return false;
+  }
+  p->bits = dev;
+  p->bits_planes = planes;
+  p->slice_gen = t->slice_gen;
+  return true;
+}
+
 // Builds the missing slices of the plan's columns and binds the plan's COUNT
 // scans to them.  Any failure leaves the plan unbound (the column scan).
 static void bind_slices(mbx_ctx* c, mbx_plan* p) {
@@ -1127,6 +1261,7 @@ static void bind_slices(mbx_ctx* c, mbx_plan* p) {
     if (!t->slices[(size_t)col].stored) {
       if (c->capturing || slice_build_col(c, t, col)) return;
     }
+  if (c->tune.auto_bitslice && bind_bits(c, p)) return;
   const KPlan& h = p->host;
   KSlicePlan sp;
   memset(&sp, 0, sizeof(sp));
@@ -1150,17 +1285,7 @@ static void bind_slices(mbx_ctx* c, mbx_plan* p) {
     slice_bound_of(st.khi, true, sl, &shi, &dhi);
     st.meta = slice_term_meta(kt.lhs, kt.rneg, slo, shi, dlo, dhi);
   }
-  // the required conjuncts: one term mask each; one without terms selects no row
-  for (uint32_t bit = 1; bit; bit <<= 1) {
-    if (!(h.all_conj & bit)) continue;
-    uint32_t m = 0;
-    for (int32_t i = 0; i < h.nterms; i++)
-      if (h.terms[i].conj_bit == bit) m |= 1u << i;
-    if (!m)
-      sp.never = 1;
-    else
-      sp.cmask[sp.nconj++] = m;
-  }
+  slice_conjuncts(h, sp.cmask, &sp.nconj, &sp.never);
   KSlicePlan* dev = nullptr;
   if (hipMalloc(&dev, sizeof(KSlicePlan)) != hipSuccess) {
     (void)hipGetLastError();
@@ -1202,6 +1327,7 @@ extern "C" int mbx_plan_free(mbx_plan* p) {
   hipStreamSynchronize(p->ctx->stream);
   for (auto& v : p->variants) hipFree(v.dev);
   hipFree(p->sliced);
+  hipFree(p->bits);
   delete p;
   return MBX_OK;
 }
@@ -1224,28 +1350,56 @@ static int32_t ticket_groups_of(const mbx_ctx* c) {
 
 // COUNT launches of a plan take the sliced kernel while the table's slices are
 // the generation the plan was bound to (mbx_table_slice drops / rebuilds bump it)
-static bool plan_sliced_now(const mbx_plan* p) { return p->sliced && p->slice_gen == p->t->slice_gen; }
+static bool plan_sliced_now(const mbx_plan* p) {
+  return (p->sliced || p->bits) && p->slice_gen == p->t->slice_gen;
+}
+// how COUNT launches of the plan read the table now (mbx_plan_slice_form)
+enum SliceForm : int32_t { kFormColumns = 0, kFormBytes = 1, kFormBits = 2 };
+static int32_t plan_form_now(const mbx_plan* p) {
+  return !plan_sliced_now(p) ? kFormColumns : (p->bits ? kFormBits : kFormBytes);
+}
 
-// Segment size and grid of the plan's COUNT launch; true: the sliced kernel,
-// whose segments count 1024-row tiles.  It runs twice the column scan's blocks
+// Segment size and grid of the plan's COUNT launch, and its SliceForm; form 1:
+// the sliced kernel, whose segments count 1024-row tiles.  It runs twice the column scan's blocks
 // (~2048, 8 waves per SIMD): a tile that needs a deeper plane waits for that
 // load with nothing else of its wave in flight, and the second set of waves
 // covers it -- 100 M rows, builder box: `c == 12345` 64.8 -> 51.6 us,
 // `c < 104858` 55.6 -> 44.8, C3 (one plane per column) 44.9 -> 41.0.  At least
 // 16 tiles per block (4 per wave: one full group of tiles in flight); the
 // tiles_per_block knob keeps its meaning in rows (4 x 256 = one sliced tile).
-static bool count_geometry(const mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int64_t* tpb, int64_t* nb) {
+//
+// The bit-plane kernel (form 2) counts 8192-row tiles and its grid follows the
+// planes the plan reads, not the rows: a tile costs one 1 KiB wave load per
+// plane (plus one of the deleted image), and a block is given kBitLoadsPerBlock
+// of them, within kBitMinBlocks .. kBitMaxBlocks blocks (DESIGN.md section 5 has
+// the sweep) and at least one tile per wave.
+constexpr int64_t kBitLoadsPerBlock = 48, kBitMinBlocks = 256, kBitMaxBlocks = 1024;
+static int32_t count_geometry(const mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int64_t* tpb, int64_t* nb) {
   *tpb = scan_tiles_per_block(c, p->t->nrows, v);
-  if (plan_sliced_now(p)) {
+  const int32_t form = plan_form_now(p);
+  if (form == kFormBits) {
+    const int64_t ntiles = (p->t->nrows + kBitTileRows - 1) / kBitTileRows;
+    if (c->tune.tiles_per_block > 0) {
+      *tpb = (*tpb + 31) / 32;
+    } else {
+      const int64_t loads = ntiles * std::max<int64_t>(p->bits_planes + (p->t->deleted ? 1 : 0), 1);
+      const int64_t blocks = std::min(std::max((loads + kBitLoadsPerBlock - 1) / kBitLoadsPerBlock, kBitMinBlocks),
+                                      kBitMaxBlocks);
+      *tpb = std::max<int64_t>((ntiles + blocks - 1) / blocks, kWaves);
+    }
+    *nb = bits_grid_blocks(p->t->nrows, *tpb);
+    return form;
+  }
+  if (form == kFormBytes) {
     if (c->tune.tiles_per_block > 0)
       *tpb = (*tpb + 3) / 4;
     else
       *tpb = std::max<int64_t>((*tpb + 7) / 8, 16);
     *nb = sliced_grid_blocks(p->t->nrows, *tpb);
-    return true;
+    return form;
   }
   *nb = grid_blocks(p->t->nrows, *tpb);
-  return false;
+  return form;
 }
 
 extern "C" int mbx_plan_sliced(mbx_ctx* c, const mbx_plan* p, int32_t* sliced) {
@@ -1253,6 +1407,14 @@ extern "C" int mbx_plan_sliced(mbx_ctx* c, const mbx_plan* p, int32_t* sliced) {
   NOTNULL(p);
   NOTNULL(sliced);
   *sliced = plan_sliced_now(p) ? 1 : 0;
+  return MBX_OK;
+}
+
+extern "C" int mbx_plan_slice_form(mbx_ctx* c, const mbx_plan* p, int32_t* form) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(form);
+  *form = plan_form_now(p);
   return MBX_OK;
 }
 
@@ -1265,9 +1427,11 @@ struct FusedSelect {
 static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode, uint64_t* out_words,
                         Partial* parts, int64_t tpb, int64_t* count_out, AggOut* agg_out, int32_t* nan_out,
                         int64_t* seg_counts = nullptr, const FusedSelect* fused = nullptr,
-                        bool need_count = true, bool frame = false, bool sliced = false) {
-  // sliced: tpb counts sliced tiles and the launch is k_scan_sliced over the plan's slices
-  const int64_t nb = sliced ? sliced_grid_blocks(p->t->nrows, tpb) : grid_blocks(p->t->nrows, tpb);
+                        bool need_count = true, bool frame = false, int32_t form = kFormColumns) {
+  // form 1 / 2: tpb counts sliced / bit tiles and the launch is k_scan_sliced / k_scan_bits over the plan's slices
+  const int64_t nb = form == kFormBits    ? bits_grid_blocks(p->t->nrows, tpb)
+                     : form == kFormBytes ? sliced_grid_blocks(p->t->nrows, tpb)
+                                          : grid_blocks(p->t->nrows, tpb);
   ScanLaunch L;
   L.plan = v.dev;
   L.nrows = p->t->nrows;
@@ -1347,7 +1511,10 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                               c->tune.select_dbg >> 4, c->tune.scan_select_waves, c->tune.select_flag_stride));
     return MBX_OK;
   }
-  if (sliced) {
+  if (form == kFormBits) {
+    L.bp = p->bits;
+    HIPCHK(launch_scan_bits(L, c->stream));
+  } else if (form == kFormBytes) {
     L.sl = p->sliced;
     HIPCHK(launch_scan_sliced(L, p->sliced_ncols, c->stream));
   } else {
@@ -1363,10 +1530,10 @@ static int scan_to_count(mbx_ctx* c, mbx_plan* p, int64_t* dev_count, int32_t* d
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
   int64_t tpb, nb;
-  const bool sliced = count_geometry(c, p, *v, &tpb, &nb);
+  const int32_t form = count_geometry(c, p, *v, &tpb, &nb);
   if ((rc = ensure_partials(c, nb))) return rc;
   return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_count, nullptr, dev_nan, nullptr, nullptr,
-                      true, false, sliced);
+                      true, false, form);
 }
 
 // NaN words: the *_async entry points report through dnan[0..1] ([1] sticky
@@ -1438,13 +1605,13 @@ extern "C" int mbx_scan_count_frame_async(mbx_ctx* c, const mbx_plan* pc, int64_
   PlanVariant* v = nullptr;
   if ((rc = plan_variant(p, -1, &v))) return rc;
   int64_t tpb, nb;
-  const bool sliced = count_geometry(c, p, *v, &tpb, &nb);
+  const int32_t form = count_geometry(c, p, *v, &tpb, &nb);
   if ((nb + kFrameSlots - 1) / kFrameSlots > kFrameMaxArrivalsPerSlot || p->t->nrows >= (int64_t(1) << 36))
     return fail(MBX_E_INVALID, "scan_count_frame: %lld rows in %lld blocks do not fit a count frame",
                 (long long)p->t->nrows, (long long)nb);
   if ((rc = ensure_partials(c, nb))) return rc;
   return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_frame, nullptr, c->dnan, nullptr, nullptr,
-                      true, true, sliced);
+                      true, true, form);
 }
 
 extern "C" int mbx_count_frame_fits(int64_t nblocks, int32_t nranks) {

@@ -158,6 +158,8 @@ struct ScanLaunch {
                               // compare, 2 literal compares of any type (int / float / char(16))
   const struct KSlicePlan* sl = nullptr;  // sliced COUNT scan (k_scan_sliced): device; tiles_per_block
                                           // then counts sliced tiles (kSliceTileRows rows)
+  const struct KBitPlan* bp = nullptr;    // bit-plane COUNT scan (k_scan_bits): device; tiles_per_block
+                                          // then counts bit tiles (kBitTileRows rows)
 };
 
 // ---- byte-plane slices of int32 columns (mbx_table_slice)
@@ -197,6 +199,89 @@ struct KSlicePlan {
   int32_t first[kSliceMaxCols];          // its plane number (4 - stored planes)
   int64_t pstride;                       // bytes between planes (rows padded to a whole tile)
   KSliceTerm terms[kSliceMaxTerms];
+};
+
+// ---- bit planes of int32 columns (BitWeaving/V)
+// The bit key of a row is k - base (k its key as above).  base is 0 and the
+// range [kmin, kmax] as sliced, except for a range of < 256 keys whose min and
+// max differ in a bit above 7 (it crosses a power of two: [-5, 4]), where
+// base = kmin.  h = the highest bit on which the bit keys of min and max
+// differ (-1: a constant column), W = min(8, h + 1) planes are kept: plane j
+// holds bit h - j of every row's bit key, row r at bit r & 31 of dword r >> 5,
+// zero bits up to a whole bit tile.  A bit tile is 8192 rows per wave: one
+// 16-byte load per lane per plane, 128 consecutive rows per lane.
+constexpr int kBitTileRows = 8192;
+constexpr int kBitMaxPlanes = 8;
+
+struct BitRange {
+  uint32_t base;  // subtracted from a key
+  int32_t h;      // highest varying bit of the bit keys, -1: constant
+  int32_t w;      // planes kept
+};
+inline BitRange bit_range_of(uint32_t kmin, uint32_t kmax) {
+  BitRange r{0u, -1, 0};
+  uint32_t x = kmin ^ kmax;
+  if (kmax - kmin < 256u && x >= 256u) {
+    r.base = kmin;
+    x = kmax - kmin;
+  }
+  while (x) {
+    r.h++;
+    x >>= 1;
+  }
+  r.w = r.h + 1 < kBitMaxPlanes ? r.h + 1 : kBitMaxPlanes;
+  return r;
+}
+
+// One bound `k >= key` (upper: `k <= key`) against a column of key range
+// [kmin, kmax]: *state as SliceState; for kSliceEqual, *depth = the bits below
+// and including h that decide it -- rows still equal to the bound after depth
+// bits hold it (a lower bound's remaining bits are all 0, an upper bound's all
+// 1); *bits = those bits of the bound's bit key, bit j = bit h - j.
+inline void bit_bound_of(uint32_t kmin, uint32_t kmax, uint32_t key, bool upper, int32_t* state, int32_t* depth,
+                         uint32_t* bits) {
+  *depth = 0;
+  *bits = 0;
+  if (upper ? key >= kmax : key <= kmin) {
+    *state = kSliceHolds;
+    return;
+  }
+  if (upper ? key < kmin : key > kmax) {
+    *state = kSliceFails;
+    return;
+  }
+  // kmin < key <= kmax (upper: kmin <= key < kmax): the bits above h agree
+  const BitRange r = bit_range_of(kmin, kmax);
+  const uint32_t b = key - r.base;
+  int32_t t = 0;
+  while (t <= r.h && ((b >> t) & 1u) == (upper ? 1u : 0u)) t++;
+  *state = kSliceEqual;
+  *depth = r.h + 1 - t;
+  for (int32_t j = 0; j < *depth && j < 32; j++) *bits |= ((b >> (r.h - j)) & 1u) << j;
+}
+
+// One term of a bit-plane COUNT plan: planes = plane 0 of its column; lo / hi
+// = the bits of its bounds (bit j compares plane j); meta packs neg, slo, shi
+// (SliceState) and the depths dlo, dhi (0..8).  The term reads max(dlo, dhi)
+// planes.
+struct KBitTerm {
+  const uint32_t* planes;
+  uint32_t lo, hi;
+  uint32_t meta;
+  uint32_t pad_;
+};
+inline uint32_t bit_term_meta(int32_t neg, int32_t slo, int32_t shi, int32_t dlo, int32_t dhi) {
+  return (uint32_t)(neg != 0) | ((uint32_t)slo << 1) | ((uint32_t)shi << 3) | ((uint32_t)dlo << 5) |
+         ((uint32_t)dhi << 9);
+}
+
+struct KBitPlan {
+  int32_t nterms;
+  int32_t nconj, never;                  // as KSlicePlan
+  int32_t pad_;
+  uint32_t cmask[kSliceMaxTerms];
+  int64_t pstride;                       // dwords between planes (rows padded to a whole bit tile)
+  KBitTerm terms[kSliceMaxTerms];
 };
 
 // dynamic LDS per block for the staged BitSet (4 blocks per CU: <= 128 KB of
@@ -380,6 +465,13 @@ hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, 
 // pstride = rows padded to a whole sliced tile, the padding written as 0)
 hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, int64_t pstride, uint8_t* out,
                               hipStream_t s);
+// bit-plane COUNT scan: L.bp set, L.tiles_per_block in bit tiles
+int64_t bits_grid_blocks(int64_t nrows, int64_t tiles_per_block);
+hipError_t launch_scan_bits(const ScanLaunch& L, hipStream_t s);
+// planes 0..w-1 (bits h..h-w+1 of key - base) of the column into out, plane j at
+// out + j * pstride dwords; pstride = rows padded to a whole bit tile / 32, the padding written as 0
+hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,
+                                 int64_t pstride, uint32_t* out, hipStream_t s);
 hipError_t launch_finalize(const Partial* partials, int64_t nblocks, int32_t agg_kind, AggOut* out,
                            int64_t* count_out, int32_t* nan_flag, hipStream_t s);
 // one launch: words of the CNF (never stored) -> positions (ids may be null)

@@ -2675,7 +2675,248 @@ __global__ __launch_bounds__(kBlock) void k_slice_build(const int32_t* __restric
   }
 }
 
+// --------------------------------------------------- bit-plane COUNT scan
+//
+// COUNT over bit planes (KBitPlan, BitWeaving/V): a wave's tile is 8192 rows,
+// one 16-byte load per lane per plane (128 consecutive rows per lane, row r at
+// bit r & 31 of dword r >> 5 -- the deleted image's order, so live rows AND
+// straight in).  The host decided how many planes each term's bounds need, so
+// every load is known at launch: no ballot, no early stop.  Plane 0 of every
+// term is loaded up front for U tiles; a term then walks its planes top-down,
+// the next plane in flight while the current one is compared.  A bound keeps
+// `ok` (rows that already hold it) and `eq` (rows equal to it so far) as
+// 128-bit row masks; its bits and depth are scalars and a step is branch-free.
+typedef __attribute__((address_space(1))) const uint32_t gu32;
+
+__device__ __forceinline__ bool bit_neg(uint32_t m) { return m & 1u; }
+__device__ __forceinline__ int32_t bit_slo(uint32_t m) { return (int32_t)((m >> 1) & 3u); }
+__device__ __forceinline__ int32_t bit_shi(uint32_t m) { return (int32_t)((m >> 3) & 3u); }
+__device__ __forceinline__ int bit_dlo(uint32_t m) { return (int)((m >> 5) & 15u); }
+__device__ __forceinline__ int bit_dhi(uint32_t m) { return (int)((m >> 9) & 15u); }
+
+__device__ __forceinline__ v4u bit_splat(uint32_t f) {
+  v4u v = {f, f, f, f};
+  return v;
+}
+
+// plane j (x) against bit j of the bound `k >= bits` (UPPER: `k <= bits`) of
+// depth d.  y: the rows beyond the bound on this bit, were the bound's bit the
+// other value -- a lower bound's 1 / an upper bound's 0 lets only equal rows
+// go on (n = 0), the other value also passes the rows beyond it (n = ~0).
+template <bool UPPER>
+__device__ __forceinline__ void bit_step(v4u& ok, v4u& eq, const v4u& x, uint32_t bits, int j, int d) {
+  const uint32_t a = j < d ? ~0u : 0u;
+  const uint32_t n = (((bits >> j) & 1u) != (UPPER ? 1u : 0u)) ? 0u : ~0u;
+  const v4u y = UPPER ? ~x : x;
+  ok |= eq & y & bit_splat(n & a);
+  eq &= (y ^ bit_splat(n)) | bit_splat(~a);
+}
+
+__device__ __forceinline__ uint32_t bit_popc(const v4u& v) {
+  return (uint32_t)(__popc(v[0]) + __popc(v[1]) + __popc(v[2]) + __popc(v[3]));
+}
+
+struct BitTerms {
+  const uint32_t* pl[kSliceMaxTerms];
+  uint32_t lo[kSliceMaxTerms], hi[kSliceMaxTerms], meta[kSliceMaxTerms];
+  int nterms;
+  int64_t pstride;
+};
+
+// The selected rows of U tiles; dw[u]: the lane's first dword of tile u in every plane
+template <int U>
+__device__ __forceinline__ void bits_eval(const BitTerms& T, const SliceCnf& cn, const int64_t (&dw)[U],
+                                          v4u (&res)[U]) {
+  v4u x0[kSliceMaxTerms][U], r[kSliceMaxTerms][U];
+#pragma unroll
+  for (int ti = 0; ti < kSliceMaxTerms; ++ti) {
+    const bool reads = ti < T.nterms && max(bit_dlo(T.meta[ti]), bit_dhi(T.meta[ti])) > 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      r[ti][u] = bit_splat(0u);
+      x0[ti][u] = bit_splat(0u);
+      if (reads) x0[ti][u] = __builtin_nontemporal_load((gv4u*)(T.pl[ti] + dw[u]));
+    }
+  }
+#pragma unroll
+  for (int ti = 0; ti < kSliceMaxTerms; ++ti)
+    if (ti < T.nterms) {
+      const uint32_t m = T.meta[ti];
+      const int dlo = bit_dlo(m), dhi = bit_dhi(m), depth = max(dlo, dhi);
+      v4u lok[U], leq[U], hok[U], heq[U], cur[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        lok[u] = bit_splat(bit_slo(m) == kSliceHolds ? ~0u : 0u);
+        leq[u] = bit_splat(bit_slo(m) == kSliceEqual ? ~0u : 0u);
+        hok[u] = bit_splat(bit_shi(m) == kSliceHolds ? ~0u : 0u);
+        heq[u] = bit_splat(bit_shi(m) == kSliceEqual ? ~0u : 0u);
+        cur[u] = x0[ti][u];
+      }
+      for (int j = 0; j < depth; ++j) {
+        v4u nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          nxt[u] = cur[u];
+          if (j + 1 < depth)
+            nxt[u] = __builtin_nontemporal_load((gv4u*)(T.pl[ti] + (int64_t)(j + 1) * T.pstride + dw[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          bit_step<false>(lok[u], leq[u], cur[u], T.lo[ti], j, dlo);
+          bit_step<true>(hok[u], heq[u], cur[u], T.hi[ti], j, dhi);
+          cur[u] = nxt[u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const v4u v = (lok[u] | leq[u]) & (hok[u] | heq[u]);
+        r[ti][u] = bit_neg(m) ? ~v : v;
+      }
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    v4u a = bit_splat(cn.never ? 0u : ~0u);
+#pragma unroll
+    for (int q = 0; q < kSliceMaxTerms; ++q)
+      if (q < cn.nconj) {
+        v4u o = bit_splat(0u);
+#pragma unroll
+        for (int ti = 0; ti < kSliceMaxTerms; ++ti)
+          if ((cn.cmask[q] >> ti) & 1u) o |= r[ti][u];
+        a &= o;
+      }
+    res[u] = a;
+  }
+}
+
+// U tiles in flight per wave; a block owns a contiguous segment of bit tiles
+// dealt round-robin to its 4 waves (as scan_sliced_body).  The planes are
+// padded to a whole tile, so the table's partial tile loads like any other and
+// masks its rows; the deleted image is padded to 64 rows only, so the partial
+// tile reads it dword by dword and never past the table's last row.
+template <bool DEL, int U>
+__global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
+  const KBitPlan* __restrict__ B = L.bp;
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)uniform(threadIdx.x >> 6);
+  const int64_t nrows = L.nrows;
+  const int64_t ntiles = (nrows + kBitTileRows - 1) / kBitTileRows;
+  const int64_t t0 = (int64_t)blockIdx.x * L.tiles_per_block;
+  const int64_t t1 = min(t0 + L.tiles_per_block, ntiles);
+  BitTerms T;
+  T.nterms = B->nterms;
+  T.pstride = B->pstride;
+#pragma unroll
+  for (int ti = 0; ti < kSliceMaxTerms; ++ti) {
+    T.pl[ti] = B->terms[ti].planes;
+    T.lo[ti] = B->terms[ti].lo;
+    T.hi[ti] = B->terms[ti].hi;
+    T.meta[ti] = B->terms[ti].meta;
+  }
+  SliceCnf cn;
+  cn.nconj = B->nconj;
+  cn.never = B->never;
+#pragma unroll
+  for (int q = 0; q < kSliceMaxTerms; ++q) cn.cmask[q] = B->cmask[q];
+  constexpr int kTileDwords = kBitTileRows / 32;
+  gu32* del = (gu32*)L.deleted;
+  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(L.deleted) & 15) == 0;  // uniform
+
+  uint32_t cnt = 0;
+  const int64_t tf = min(t1, nrows / kBitTileRows);  // full tiles in the main loop
+  for (int64_t base = t0 + wave; base < tf; base += (int64_t)kWaves * U) {
+    int64_t dw[U];
+    v4u dead[U], res[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // clamped: every path issues the same loads
+      int64_t t = base + (int64_t)u * kWaves;
+      t = t < tf ? t : tf - 1;
+      dw[u] = t * kTileDwords + lane * 4;
+      if (DEL) {
+        if (del16) {
+          dead[u] = __builtin_nontemporal_load((gv4u*)(del + dw[u]));
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dead[u][i] = del[dw[u] + i];
+        }
+      }
+    }
+    bits_eval<U>(T, cn, dw, res);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (base + (int64_t)u * kWaves < tf) cnt += bit_popc(DEL ? res[u] & ~dead[u] : res[u]);
+  }
+  const int64_t tp = nrows / kBitTileRows;  // the partial tile, owned like any other tile of [t0, t1)
+  if ((nrows % kBitTileRows) != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
+    int64_t dw[1] = {tp * kTileDwords + lane * 4};
+    v4u live, res[1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t rem = nrows - (dw[0] + i) * 32;  // the dword's rows below nrows
+      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << (int)rem) - 1u));
+      if (DEL && rem > 0) valid &= ~del[dw[0] + i];
+      live[i] = valid;
+    }
+    bits_eval<1>(T, cn, dw, res);
+    cnt += bit_popc(res[0] & live);
+  }
+  uint64_t wc = cnt;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) wc += __shfl_xor(wc, m);
+  Acc acc;
+  acc_init(acc);
+  acc.count = lane == 0 ? (int64_t)wc : 0;
+  block_reduce_store<false>(acc, L);
+}
+
+// planes 0..w-1 of 64 rows per wave step: one ballot per plane, lane j stores
+// plane j's 64 bits (rows past nrows, up to the padded plane length, as 0)
+__global__ __launch_bounds__(kBlock) void k_bitslice_build(const int32_t* __restrict__ col, int64_t nrows,
+                                                           uint32_t base, int32_t h, int32_t w, int64_t pstride,
+                                                           uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ngroups = pstride / 2;  // 64-row groups of a padded plane
+  const int64_t nw = (int64_t)gridDim.x * kWaves;
+  for (int64_t g = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); g < ngroups; g += nw) {
+    const int64_t r = g * 64 + lane;
+    const bool in = r < nrows;
+    const uint32_t k = in ? ((uint32_t)col[r] ^ 0x80000000u) - base : 0u;
+    uint64_t mine = 0;
+    for (int j = 0; j < w; ++j) {
+      const uint64_t b = __builtin_amdgcn_ballot_w64(in && ((k >> (h - j)) & 1u) != 0u);
+      if (lane == j) mine = b;
+    }
+    if (lane < w) reinterpret_cast<uint64_t*>(out + (int64_t)lane * pstride)[g] = mine;
+  }
+}
+
 // ---------------------------------------------------------------- launchers
+
+int64_t bits_grid_blocks(int64_t nrows, int64_t tiles_per_block) {
+  const int64_t ntiles = (nrows + kBitTileRows - 1) / kBitTileRows;
+  const int64_t g = (ntiles + tiles_per_block - 1) / tiles_per_block;
+  return g < 1 ? 1 : g;
+}
+
+#ifndef MBX_BITS_U
+#define MBX_BITS_U 2
+#endif
+hipError_t launch_scan_bits(const ScanLaunch& L, hipStream_t s) {
+  const dim3 grid((unsigned)bits_grid_blocks(L.nrows, L.tiles_per_block));
+  if (L.deleted)
+    hipLaunchKernelGGL((k_scan_bits<true, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+  else
+    hipLaunchKernelGGL((k_scan_bits<false, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+  return hipGetLastError();
+}
+
+hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,
+                                 int64_t pstride, uint32_t* out, hipStream_t s) {
+  int64_t g = (pstride / 2 + kWaves - 1) / kWaves;
+  g = g < 1 ? 1 : (g > 8192 ? 8192 : g);
+  hipLaunchKernelGGL(k_bitslice_build, dim3((unsigned)g), dim3(kBlock), 0, s, col, nrows, base, h, w, pstride, out);
+  return hipGetLastError();
+}
 
 int64_t sliced_grid_blocks(int64_t nrows, int64_t tiles_per_block) {
   const int64_t ntiles = (nrows + kSliceTileRows - 1) / kSliceTileRows;

@@ -73,6 +73,8 @@ struct MbxTuning {
   int32_t comm_same_stream = 1;   // MBX_COMM_SAME_STREAM: collectives on the context stream (0: the exchange stream)
   int32_t auto_slice = 1;         // MBX_AUTO_SLICE: mbx_plan_compile builds byte-plane slices of the int32 columns of a
                                   // slice-eligible plan and binds its COUNT scans to them (0: plans read the columns)
+  int32_t auto_bitslice = 1;      // MBX_AUTO_BITSLICE: a sliced plan whose every bound is decided within its column's
+                                  // bit planes binds to those (k_scan_bits); 0: every sliced plan takes the byte planes
   int32_t select_dbg = 0;         // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
                                   // instead of the chained look-back, 512 write-through flip; -DMBX_DIAG
                                   // builds only: k_select_ids bit 0 no prefix / bit 1 no emission, the
@@ -120,6 +122,11 @@ struct TSlice {
   int32_t first = 4;
   uint32_t kmin = 0, kmax = 0;  // key range of the column when it was sliced
   uint8_t* dev = nullptr;
+  // bit planes of the same key range (mbx_internal.hpp bit_range_of), built by
+  // the first bit-decidable plan that reads the column: bit_w planes at bdev,
+  // one bit-tile-padded plane after the other; bit_w < 0: not built
+  int32_t bit_w = -1;
+  uint32_t* bdev = nullptr;
 };
 
 struct mbx_table {
@@ -159,6 +166,10 @@ struct mbx_plan {
   mbx::KSlicePlan* sliced = nullptr;
   int32_t sliced_ncols = 0;
   uint64_t slice_gen = 0;
+  // bit-plane COUNT scan (k_scan_bits) instead: the device plan over the
+  // slices' bit planes (sliced is then null), and the planes it reads per tile
+  mbx::KBitPlan* bits = nullptr;
+  int32_t bits_planes = 0;
 };
 
 struct mbx_bitmap {

@@ -80,7 +80,8 @@ def java_mutf8(s):
 
 EXPORTS = [
     "mbx_abi_version", "mbx_last_error", "mbx_device_count", "mbx_init", "mbx_free", "mbx_sync", "mbx_stream",
-    "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_table_slice", "mbx_table_slice_info", "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced",
+    "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_table_slice", "mbx_table_slice_info", "mbx_table_bitslice_info", "mbx_bitslice_range", "mbx_bitslice_bound",
+    "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced", "mbx_plan_slice_form",
     "mbx_scan_count", "mbx_scan_count_async", "mbx_scan_count_frame_async", "mbx_count_frame_decode",
     "mbx_count_frame_fits",
     "mbx_scan_blocks", "mbx_scan_bitmap", "mbx_scan_bitmap_async", "mbx_scan_select",
@@ -153,6 +154,11 @@ def lib():
         "mbx_table_slice": ([V, V, P(I32), I32], ctypes.c_int),
         "mbx_table_slice_info": ([V, I32, P(I32)], ctypes.c_int),
         "mbx_plan_sliced": ([V, V, P(I32)], ctypes.c_int),
+        "mbx_plan_slice_form": ([V, V, P(I32)], ctypes.c_int),
+        "mbx_table_bitslice_info": ([V, I32, P(I32)], ctypes.c_int),
+        "mbx_bitslice_range": ([ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32), P(I32), P(I32)], ctypes.c_int),
+        "mbx_bitslice_bound": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, I32, P(I32), P(I32)],
+                               ctypes.c_int),
         "mbx_plan_compile": ([V, V, P(Cnf), P(V)], ctypes.c_int),
         "mbx_plan_free": ([V], ctypes.c_int),
         "mbx_scan_count": ([V, V, P(I64)], ctypes.c_int),
@@ -431,6 +437,19 @@ class Context:
         n = ctypes.c_int32()
         _chk(lib().mbx_plan_sliced(self.h, plan.h, ctypes.byref(n)))
         return bool(n.value)
+
+    def plan_slice_form(self, plan):
+        """mbx_plan_slice_form: what the plan's COUNT launches read now -- 0 the
+        columns, 1 byte planes, 2 bit planes."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_plan_slice_form(self.h, plan.h, ctypes.byref(n)))
+        return n.value
+
+    def bitslice_info(self, table, col):
+        """mbx_table_bitslice_info: the bit planes column `col` keeps (0: none)."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_table_bitslice_info(table.h, col, ctypes.byref(n)))
+        return n.value
 
     def join(self, outer, outer_sel, inner, inner_sel, cnf, order, outer_block=0):
         """mbx_join: cnf = [[(op, outer_col, inner_col), ...], ...] (0-based
@@ -757,6 +776,20 @@ def count_frame_decode(frame):
 def count_frame_fits(nblocks, nranks):
     """mbx_count_frame_fits: nranks frames of <= nblocks-block scans sum exactly."""
     return bool(lib().mbx_count_frame_fits(int(nblocks), int(nranks)))
+
+
+def bitslice_range(kmin, kmax):
+    """mbx_bitslice_range: (base, high_bit, bits) of a column whose keys span [kmin, kmax]."""
+    b, h, w = ctypes.c_uint32(), ctypes.c_int32(), ctypes.c_int32()
+    _chk(lib().mbx_bitslice_range(kmin, kmax, ctypes.byref(b), ctypes.byref(h), ctypes.byref(w)))
+    return b.value, h.value, w.value
+
+
+def bitslice_bound(kmin, kmax, key, upper):
+    """mbx_bitslice_bound: (state, depth) of the bound `k >= key` (upper: `k <= key`)."""
+    st, d = ctypes.c_int32(), ctypes.c_int32()
+    _chk(lib().mbx_bitslice_bound(kmin, kmax, key, 1 if upper else 0, ctypes.byref(st), ctypes.byref(d)))
+    return st.value, d.value
 
 
 def comm_unique_id():

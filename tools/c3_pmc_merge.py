@@ -8,6 +8,10 @@ read-request size split, write = WRITE_SIZE.  C3's COUNT launches the sliced
 scan (k_scan_sliced) since the byte-plane slices: its traffic is the planes it
 reads (1 byte per row per column: the entry's algorithmic bytes), beside the
 8 bytes per row of the columns that bench.py's hbm_gbs divides by the time.
+Since the bit planes C3's COUNT launches k_scan_bits, which reads 1 bit per row
+per column (2 x ceil(rows / 8192) KiB); a session taken on it lands under each
+entry's `remeasured_bits` and leaves the entry itself (what roofline.traffic
+reports) as it is.  Shard sizes the session does not hold are skipped.
     python3 tools/c3_pmc_merge.py DIR [NOTE]"""
 import json
 import os
@@ -29,11 +33,27 @@ def main():
                          ("n8", 8, "frame")):
         s, e = mbx.shard_bounds(100_000_000, n, 0)
         rows = e - s
-        k = [json.loads(x) for x in open(os.path.join(src, f"{tag}_kernels.jsonl")) if "k_scan_sliced" in x]
+        f = os.path.join(src, f"{tag}_kernels.jsonl")
+        if not os.path.exists(f):
+            continue
+        k = [json.loads(x) for x in open(f) if "k_scan_sliced" in x or "k_scan_bits" in x]
         assert len(k) == 1, (n, [x["kernel"] for x in k])
         k = k[0]
         assert k.get("read_basis") == "request split", k
         hbm = (k["read_MB"] + k["write_MB"]) * 1e6
+        key = f"{rows}:{mode}"
+        if "k_scan_bits" in k["kernel"]:
+            alg = 2 * -(-rows // 8192) * 1024
+            d["shards"][key]["remeasured_bits"] = {
+                "kernel_substr": "k_scan_bits", "kernel": k["kernel"], "rows": rows, "gpus": n,
+                "dispatches_traced": k["dispatches"], "avg_duration_ns": k["avg_us"] * 1e3,
+                "median_duration_ns": k["median_us"] * 1e3, "read_bytes_per_launch": k["read_MB"] * 1e6,
+                "write_bytes_per_launch": k["write_MB"] * 1e6, "hbm_bytes_per_launch": hbm,
+                "algorithmic_bytes_per_launch": alg, "traffic_over_algorithmic": hbm / alg,
+                "read_128B_share": k.get("read_128B_share"),
+                "correction": "read bytes from gfx950's request-size split, write = WRITE_SIZE x 1024; algorithmic = "
+                              "the bit planes C3 reads, one 1 KiB wave load per 8192-row tile per column"}
+            continue
         rec = {
             "kernel_substr": "k_scan_sliced", "kernel": k["kernel"], "rows": rows, "gpus": n,
             "dispatches_traced": k["dispatches"], "avg_duration_ns": k["avg_us"] * 1e3,
@@ -44,7 +64,6 @@ def main():
             "read_128B_share": k.get("read_128B_share"),
             "correction": "read bytes from gfx950's request-size split, write = WRITE_SIZE x 1024; algorithmic = the "
                           "planes C3 reads, 1 byte per row per column"}
-        key = f"{rows}:{mode}"
         # an entry feeds roofline.traffic and is held to 0.2 % of its algorithmic bytes
         # (tests/test_bench_launch.py).  The sliced launch moves a fixed ~0.2 MB beyond its planes; on the
         # small strong-scaling shards that is more than 0.2 % of 2 bytes per row, so their column-scan

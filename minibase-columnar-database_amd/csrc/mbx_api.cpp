@@ -500,151 +500,6 @@ extern "C" int mbx_table_group(mbx_ctx* c, mbx_table* t, const int32_t* cols, in
   return MBX_OK;
 }
 
-// Byte-plane slices of one int32 column: the key range
-// on the device, then the planes below the range's constant prefix.  One read
-// of the column and a write of <= 4 bytes per row; synchronous.
-static int slice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
-  const int32_t* src = (const int32_t*)t->cols[(size_t)col].dev;
-  const int64_t tiles = (t->nrows + kSliceTileRows - 1) / kSliceTileRows;
-  const int64_t pstride = (tiles < 1 ? 1 : tiles) * kSliceTileRows;
-  uint32_t* dmm = nullptr;
-  if (hipMalloc(&dmm, 2 * sizeof(uint32_t)) != hipSuccess) return fail(MBX_E_NOMEM, "table_slice: scratch");
-  uint32_t mm[2] = {~0u, 0u};
-  hipError_t e = hipMemcpyAsync(dmm, mm, sizeof(mm), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_slice_minmax(src, t->nrows, dmm, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(mm, dmm, sizeof(mm), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(dmm);
-  if (e != hipSuccess) return fail(MBX_E_DEVICE, "table_slice: %s", hipGetErrorString(e));
-  if (mm[0] > mm[1]) mm[0] = mm[1] = 0x80000000u;  // no rows
-  TSlice sl;
-  sl.kmin = mm[0];
-  sl.kmax = mm[1];
-  sl.first = 0;  // leading planes on which min and max agree; the last plane is always stored
-  while (sl.first < 3 && (mm[0] >> (24 - 8 * sl.first)) == (mm[1] >> (24 - 8 * sl.first))) sl.first++;
-  sl.stored = 4 - sl.first;
-  const size_t bytes = (size_t)sl.stored * (size_t)pstride;
-  if (hipMalloc(&sl.dev, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MBX_E_NOMEM, "table_slice: %zu bytes", bytes);
-  }
-  e = launch_slice_build(src, t->nrows, sl.first, pstride, sl.dev, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    hipFree(sl.dev);
-    return fail(MBX_E_DEVICE, "table_slice: %s", hipGetErrorString(e));
-  }
-  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
-  t->slices[(size_t)col] = sl;
-  return MBX_OK;
-}
-
-// dwords between the bit planes of a table's columns: the rows padded to a whole bit tile
-static int64_t bit_pstride(int64_t nrows) {
-  const int64_t tiles = (nrows + kBitTileRows - 1) / kBitTileRows;
-  return (tiles < 1 ? 1 : tiles) * (kBitTileRows / 32);
-}
-
-// Bit planes of a sliced column, over the slice's key range: one more read of
-// the column and a write of <= 1 byte per row; synchronous.  Adds to the
-// slice and drops nothing, so slice_gen stays.
-static int bitslice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
-  TSlice& sl = t->slices[(size_t)col];
-  const mbx::BitRange br = mbx::bit_range_of(sl.kmin, sl.kmax);
-  if (br.w == 0) {  // a constant column: every bound is decided on the host
-    sl.bit_w = 0;
-    return MBX_OK;
-  }
-  const int64_t pstride = bit_pstride(t->nrows);
-  const size_t bytes = (size_t)br.w * (size_t)pstride * sizeof(uint32_t);
-  uint32_t* dev = nullptr;
-  if (hipMalloc(&dev, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MBX_E_NOMEM, "table bit planes: %zu bytes", bytes);
-  }
-  hipError_t e = launch_bitslice_build((const int32_t*)t->cols[(size_t)col].dev, t->nrows, br.base, br.h, br.w,
-                                       pstride, dev, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    hipFree(dev);
-    return fail(MBX_E_DEVICE, "table bit planes: %s", hipGetErrorString(e));
-  }
-  sl.bdev = dev;
-  sl.bit_w = br.w;
-  return MBX_OK;
-}
-
-extern "C" int mbx_table_bitslice_info(const mbx_table* t, int32_t col, int32_t* bits) {
-  NOTNULL(t);
-  NOTNULL(bits);
-  if (col < 0 || col >= (int32_t)t->cols.size())
-    return fail(MBX_E_RANGE, "table_bitslice_info: column %d outside 0..%zu", col, t->cols.size() - 1);
-  const int32_t w = (size_t)col < t->slices.size() ? t->slices[(size_t)col].bit_w : 0;
-  *bits = w > 0 ? w : 0;
-  return MBX_OK;
-}
-
-extern "C" int mbx_bitslice_range(uint32_t kmin, uint32_t kmax, uint32_t* base, int32_t* high_bit, int32_t* bits) {
-  if (kmin > kmax) return fail(MBX_E_INVALID, "bitslice_range: kmin %u > kmax %u", kmin, kmax);
-  const mbx::BitRange br = mbx::bit_range_of(kmin, kmax);
-  if (base) *base = br.base;
-  if (high_bit) *high_bit = br.h;
-  if (bits) *bits = br.w;
-  return MBX_OK;
-}
-
-extern "C" int mbx_bitslice_bound(uint32_t kmin, uint32_t kmax, uint32_t key, int32_t upper, int32_t* state,
-                                  int32_t* depth) {
-  NOTNULL(state);
-  NOTNULL(depth);
-  if (kmin > kmax) return fail(MBX_E_INVALID, "bitslice_bound: kmin %u > kmax %u", kmin, kmax);
-  uint32_t bits;
-  mbx::bit_bound_of(kmin, kmax, key, upper != 0, state, depth, &bits);
-  return MBX_OK;
-}
-
-extern "C" int mbx_table_slice(mbx_ctx* c, mbx_table* t, const int32_t* cols, int32_t ncols) {
-  NOTNULL(c);
-  NOTNULL(t);
-  if (c->capturing) return fail(MBX_E_INVALID, "table_slice: inside a graph capture (it allocates)");
-  if (ncols < 0) return fail(MBX_E_INVALID, "table_slice: ncols = %d", ncols);
-  if (ncols > 0) NOTNULL(cols);
-  for (int32_t k = 0; k < ncols; k++) {
-    if (cols[k] < 0 || cols[k] >= (int32_t)t->cols.size())
-      return fail(MBX_E_RANGE, "table_slice: column %d outside 0..%zu", cols[k], t->cols.size() - 1);
-    if (t->cols[(size_t)cols[k]].attr_type != MBX_ATTR_INTEGER)
-      return fail(MBX_E_TYPE, "table_slice: column %d is not an int32 column", cols[k]);
-  }
-  int rc = set_device(c);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));  // no launch in flight still reads a slice
-  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
-  bool dropped = false;
-  for (size_t j = 0; j < t->slices.size(); j++) {
-    bool named = ncols == 0;  // ncols = 0: drop every slice
-    for (int32_t k = 0; k < ncols; k++) named = named || cols[k] == (int32_t)j;
-    if (named && t->slices[j].stored) {
-      hipFree(t->slices[j].dev);
-      hipFree(t->slices[j].bdev);
-      t->slices[j] = TSlice();
-      dropped = true;
-    }
-  }
-  if (dropped) t->slice_gen++;  // plans bound to the dropped slices scan the columns from now on
-  for (int32_t k = 0; k < ncols; k++)
-    if (!t->slices[(size_t)cols[k]].stored && (rc = slice_build_col(c, t, cols[k]))) return rc;
-  return MBX_OK;
-}
-
-extern "C" int mbx_table_slice_info(const mbx_table* t, int32_t col, int32_t* stored_planes) {
-  NOTNULL(t);
-  NOTNULL(stored_planes);
-  if (col < 0 || col >= (int32_t)t->cols.size())
-    return fail(MBX_E_RANGE, "table_slice_info: column %d outside 0..%zu", col, t->cols.size() - 1);
-  *stored_planes = (size_t)col < t->slices.size() ? t->slices[(size_t)col].stored : 0;
-  return MBX_OK;
-}
-
 int mbx::table_alloc(mbx_ctx* c, const mbx_col_desc* cols, int32_t ncols, int64_t nrows, int64_t row_offset,
                      bool with_deleted, mbx_table** out) {
   *out = nullptr;
@@ -1144,162 +999,6 @@ static int plan_variant(mbx_plan* p, int32_t agg_col, PlanVariant** out) {
   return MBX_OK;
 }
 
-// Sliced COUNT scan eligibility: 1..4 terms `int32 column OP int literal`
-// (either operand order: the range form normalises both) over <= 4 columns,
-// any CNF shape.  Never-true int terms are dropped by compile_into; a plan
-// that keeps no term references no column and stays on the column scan.
-static bool slice_eligible(const mbx_plan* p) {
-  const KPlan& h = p->host;
-  if (!p->all_literal || h.has_real || p->ctx->tune.force_generic) return false;
-  if (h.nterms < 1 || h.nterms > kSliceMaxTerms) return false;
-  if (p->slot_col.empty() || p->slot_col.size() > (size_t)kSliceMaxCols) return false;
-  for (int32_t i = 0; i < h.nterms; i++)
-    if (h.terms[i].kind != kInt || h.terms[i].rhs >= 0) return false;
-  for (int32_t col : p->slot_col)
-    if (p->t->cols[(size_t)col].attr_type != MBX_ATTR_INTEGER) return false;
-  return true;
-}
-
-// One bound of a term against a column's slices: its state after the
-// constant prefix and the last plane that has to compare it.  Equal rows are
-// decided once the bound's remaining bytes are all 0x00 (lower) / 0xFF
-// (upper): equal then means the bound holds.
-static void slice_bound_of(uint32_t key, bool upper, const TSlice& sl, int32_t* state, int32_t* dlast) {
-  *dlast = -1;
-  if (sl.first > 0) {
-    const int sh = 32 - 8 * sl.first;
-    const uint32_t cp = sl.kmin >> sh, bp = key >> sh;
-    if (cp != bp) {
-      *state = (upper ? cp < bp : cp > bp) ? kSliceHolds : kSliceFails;
-      return;
-    }
-  }
-  for (int p = sl.first - 1; p <= 3; p++) {
-    const uint64_t rest = (uint64_t(1) << (24 - 8 * p)) - 1;  // the bytes below plane p
-    if ((key & rest) == (upper ? (uint32_t)rest : 0u)) {
-      if (p < sl.first) {
-        *state = kSliceHolds;
-        return;
-      }
-      *state = kSliceEqual;
-      *dlast = p;
-      return;
-    }
-  }
-}
-
-// The required conjuncts of a plan as term masks (KSlicePlan / KBitPlan): one
-// without terms selects no row
-static void slice_conjuncts(const KPlan& h, uint32_t (&cmask)[kSliceMaxTerms], int32_t* nconj, int32_t* never) {
-  for (uint32_t bit = 1; bit; bit <<= 1) {
-    if (!(h.all_conj & bit)) continue;
-    uint32_t m = 0;
-    for (int32_t i = 0; i < h.nterms; i++)
-      if (h.terms[i].conj_bit == bit) m |= 1u << i;
-    if (!m)
-      *never = 1;
-    else
-      cmask[(*nconj)++] = m;
-  }
-}
-
-// Binds a slice-eligible plan whose columns are sliced to their bit planes
-// when every bound of every term is decided within the planes its column
-// keeps (bit_bound_of: depth <= W), building the planes it reads that do not
-// exist yet.  false: the plan takes the byte planes (not bit-decidable, under
-// a capture with planes missing, or no memory for planes / plan).
-static bool bind_bits(mbx_ctx* c, mbx_plan* p) {
-  const mbx_table* t = p->t;
-  const KPlan& h = p->host;
-  KBitPlan bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.nterms = h.nterms;
-  bp.pstride = bit_pstride(t->nrows);
-  int32_t depth[kSliceMaxTerms] = {0, 0, 0, 0}, planes = 0;
-  for (int32_t i = 0; i < h.nterms; i++) {
-    const KTerm& kt = h.terms[i];
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
-    const uint32_t klo = (uint32_t)kt.rlo ^ 0x80000000u, khi = klo + kt.rspan;  // as bind_slices
-    const int32_t w = mbx::bit_range_of(sl.kmin, sl.kmax).w;
-    int32_t slo, shi, dlo, dhi;
-    KBitTerm& bt = bp.terms[i];
-    mbx::bit_bound_of(sl.kmin, sl.kmax, klo, false, &slo, &dlo, &bt.lo);
-    mbx::bit_bound_of(sl.kmin, sl.kmax, khi, true, &shi, &dhi, &bt.hi);
-    if (dlo > w || dhi > w) return false;
-    bt.meta = bit_term_meta(kt.rneg, slo, shi, dlo, dhi);
-    depth[i] = std::max(dlo, dhi);
-    planes += depth[i];
-  }
-  for (int32_t i = 0; i < h.nterms; i++) {
-    if (depth[i] == 0) continue;  // no plane of its column is read for this term
-    const int32_t col = p->slot_col[(size_t)h.terms[i].lhs];
-    if (t->slices[(size_t)col].bit_w < 0 && (c->capturing || bitslice_build_col(c, t, col))) return false;
-    bp.terms[i].planes = t->slices[(size_t)col].bdev;
-  }
-  slice_conjuncts(h, bp.cmask, &bp.nconj, &bp.never);
-  KBitPlan* dev = nullptr;
-  if (hipMalloc(&dev, sizeof(KBitPlan)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (hipMemcpy(dev, &bp, sizeof(KBitPlan), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(dev);
-    return false;
-  }
-  p->bits = dev;
-  p->bits_planes = planes;
-  p->slice_gen = t->slice_gen;
-  return true;
-}
-
-// Builds the missing slices of the plan's columns and binds the plan's COUNT
-// scans to them.  Any failure leaves the plan unbound (the column scan).
-static void bind_slices(mbx_ctx* c, mbx_plan* p) {
-  const mbx_table* t = p->t;
-  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
-  for (int32_t col : p->slot_col)
-    if (!t->slices[(size_t)col].stored) {
-      if (c->capturing || slice_build_col(c, t, col)) return;
-    }
-  if (c->tune.auto_bitslice && bind_bits(c, p)) return;
-  const KPlan& h = p->host;
-  KSlicePlan sp;
-  memset(&sp, 0, sizeof(sp));
-  sp.ncols = (int32_t)p->slot_col.size();
-  sp.nterms = h.nterms;
-  const int64_t tiles = (t->nrows + kSliceTileRows - 1) / kSliceTileRows;
-  sp.pstride = (tiles < 1 ? 1 : tiles) * kSliceTileRows;
-  for (int32_t s = 0; s < sp.ncols; s++) {
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)s]];
-    sp.planes[s] = sl.dev;
-    sp.first[s] = sl.first;
-  }
-  for (int32_t i = 0; i < h.nterms; i++) {
-    const KTerm& kt = h.terms[i];
-    KSliceTerm& st = sp.terms[i];
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
-    st.klo = (uint32_t)kt.rlo ^ 0x80000000u;
-    st.khi = st.klo + kt.rspan;  // int_range_of: lo <= hi as ints, no wrap
-    int32_t slo, shi, dlo, dhi;
-    slice_bound_of(st.klo, false, sl, &slo, &dlo);
-    slice_bound_of(st.khi, true, sl, &shi, &dhi);
-    st.meta = slice_term_meta(kt.lhs, kt.rneg, slo, shi, dlo, dhi);
-  }
-  slice_conjuncts(h, sp.cmask, &sp.nconj, &sp.never);
-  KSlicePlan* dev = nullptr;
-  if (hipMalloc(&dev, sizeof(KSlicePlan)) != hipSuccess) {
-    (void)hipGetLastError();
-    return;
-  }
-  if (hipMemcpy(dev, &sp, sizeof(KSlicePlan), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(dev);
-    return;
-  }
-  p->sliced = dev;
-  p->sliced_ncols = sp.ncols;
-  p->slice_gen = t->slice_gen;
-}
-
 extern "C" int mbx_plan_compile(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_plan** out) {
   NOTNULL(c);
   NOTNULL(t);
@@ -1316,7 +1015,7 @@ extern "C" int mbx_plan_compile(mbx_ctx* c, const mbx_table* t, const mbx_cnf* c
     mbx_plan_free(p);
     return rc;
   }
-  if (c->tune.auto_slice && slice_eligible(p)) bind_slices(c, p);  // unbound on failure: the column scan
+  bind_planes(c, p);  // slice-eligible plans; unbound on failure: the column scan
   *out = p;
   return MBX_OK;
 }
@@ -1326,8 +1025,7 @@ extern "C" int mbx_plan_free(mbx_plan* p) {
   hipSetDevice(p->ctx->device);
   hipStreamSynchronize(p->ctx->stream);
   for (auto& v : p->variants) hipFree(v.dev);
-  hipFree(p->sliced);
-  hipFree(p->bits);
+  hipFree(p->planes.dev);
   delete p;
   return MBX_OK;
 }
@@ -1335,7 +1033,7 @@ extern "C" int mbx_plan_free(mbx_plan* p) {
 // ------------------------------------------------------------------- scans
 
 // kFinPackedCount's 64-bit ticket words hold < 4096 arrivals and NaN blocks
-// per word and a 40-bit count (mbx_kernels.hip, packed_count_finalize).
+// per word and a 40-bit count (mbx_device.hpp, packed_count_finalize).
 static bool packed_count_fits(int64_t nrows, int64_t nb, int32_t groups) {
   const int64_t per_word = (groups > 1 && nb > groups) ? std::max<int64_t>((nb + groups - 1) / groups, groups) : nb;
   return per_word < 4096 && nrows < (int64_t(1) << 40);
@@ -1348,90 +1046,30 @@ static int32_t ticket_groups_of(const mbx_ctx* c) {
   return g > kMaxTicketGroups ? kDefaultTicketGroups : g;
 }
 
-// COUNT launches of a plan take the sliced kernel while the table's slices are
-// the generation the plan was bound to (mbx_table_slice drops / rebuilds bump it)
-static bool plan_sliced_now(const mbx_plan* p) {
-  return (p->sliced || p->bits) && p->slice_gen == p->t->slice_gen;
-}
-// how COUNT launches of the plan read the table now (mbx_plan_slice_form)
-enum SliceForm : int32_t { kFormColumns = 0, kFormBytes = 1, kFormBits = 2 };
-static int32_t plan_form_now(const mbx_plan* p) {
-  return !plan_sliced_now(p) ? kFormColumns : (p->bits ? kFormBits : kFormBytes);
-}
-
-// Segment size and grid of the plan's COUNT launch, and its SliceForm; form 1:
-// the sliced kernel, whose segments count 1024-row tiles.  It runs twice the column scan's blocks
-// (~2048, 8 waves per SIMD): a tile that needs a deeper plane waits for that
-// load with nothing else of its wave in flight, and the second set of waves
-// covers it -- 100 M rows, builder box: `c == 12345` 64.8 -> 51.6 us,
-// `c < 104858` 55.6 -> 44.8, C3 (one plane per column) 44.9 -> 41.0.  At least
-// 16 tiles per block (4 per wave: one full group of tiles in flight); the
-// tiles_per_block knob keeps its meaning in rows (4 x 256 = one sliced tile).
-//
-// The bit-plane kernel (form 2) counts 8192-row tiles and its grid follows the
-// planes the plan reads, not the rows: a tile costs one 1 KiB wave load per
-// plane (plus one of the deleted image), and a block is given kBitLoadsPerBlock
-// of them, within kBitMinBlocks .. kBitMaxBlocks blocks (DESIGN.md section 5 has
-// the sweep) and at least one tile per wave.
-constexpr int64_t kBitLoadsPerBlock = 48, kBitMinBlocks = 256, kBitMaxBlocks = 1024;
-static int32_t count_geometry(const mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int64_t* tpb, int64_t* nb) {
-  *tpb = scan_tiles_per_block(c, p->t->nrows, v);
-  const int32_t form = plan_form_now(p);
-  if (form == kFormBits) {
-    const int64_t ntiles = (p->t->nrows + kBitTileRows - 1) / kBitTileRows;
-    if (c->tune.tiles_per_block > 0) {
-      *tpb = (*tpb + 31) / 32;
-    } else {
-      const int64_t loads = ntiles * std::max<int64_t>(p->bits_planes + (p->t->deleted ? 1 : 0), 1);
-      const int64_t blocks = std::min(std::max((loads + kBitLoadsPerBlock - 1) / kBitLoadsPerBlock, kBitMinBlocks),
-                                      kBitMaxBlocks);
-      *tpb = std::max<int64_t>((ntiles + blocks - 1) / blocks, kWaves);
-    }
-    *nb = bits_grid_blocks(p->t->nrows, *tpb);
-    return form;
-  }
-  if (form == kFormBytes) {
-    if (c->tune.tiles_per_block > 0)
-      *tpb = (*tpb + 3) / 4;
-    else
-      *tpb = std::max<int64_t>((*tpb + 7) / 8, 16);
-    *nb = sliced_grid_blocks(p->t->nrows, *tpb);
-    return form;
-  }
-  *nb = grid_blocks(p->t->nrows, *tpb);
-  return form;
-}
-
-extern "C" int mbx_plan_sliced(mbx_ctx* c, const mbx_plan* p, int32_t* sliced) {
-  NOTNULL(c);
-  NOTNULL(p);
-  NOTNULL(sliced);
-  *sliced = plan_sliced_now(p) ? 1 : 0;
-  return MBX_OK;
-}
-
-extern "C" int mbx_plan_slice_form(mbx_ctx* c, const mbx_plan* p, int32_t* form) {
-  NOTNULL(c);
-  NOTNULL(p);
-  NOTNULL(form);
-  *form = plan_form_now(p);
-  return MBX_OK;
-}
-
 // k_scan_select's extra arguments (a BitSet scan that also writes the positions)
 struct FusedSelect {
   int64_t* ids;
   int64_t* total;
 };
 
+// what a launch does beside the scan itself
+struct ScanOpts {
+  int64_t* seg_counts = nullptr;        // BitSet scans: the output bitmap's per-segment counts
+  const FusedSelect* fused = nullptr;   // k_scan_select
+  bool need_count = true;               // false: nobody reads the count from this launch
+  bool frame = false;                   // count_out is a count frame (mbx_scan_count_frame_async)
+};
+
+// the grid of a scan over the columns, tpb 256-row tiles per block
+static ScanGeometry column_geometry(const mbx_plan* p, int64_t tpb) {
+  return ScanGeometry{kFormColumns, tpb, grid_blocks(p->t->nrows, tpb)};
+}
+
 static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode, uint64_t* out_words,
-                        Partial* parts, int64_t tpb, int64_t* count_out, AggOut* agg_out, int32_t* nan_out,
-                        int64_t* seg_counts = nullptr, const FusedSelect* fused = nullptr,
-                        bool need_count = true, bool frame = false, int32_t form = kFormColumns) {
-  // form 1 / 2: tpb counts sliced / bit tiles and the launch is k_scan_sliced / k_scan_bits over the plan's slices
-  const int64_t nb = form == kFormBits    ? bits_grid_blocks(p->t->nrows, tpb)
-                     : form == kFormBytes ? sliced_grid_blocks(p->t->nrows, tpb)
-                                          : grid_blocks(p->t->nrows, tpb);
+                        Partial* parts, const ScanGeometry& g, int64_t* count_out, AggOut* agg_out,
+                        int32_t* nan_out, const ScanOpts& o = ScanOpts()) {
+  // g.form kFormBytes / kFormBits: g.tpb counts sliced / bit tiles and the launch is the plan's plane scan
+  const int64_t tpb = g.tpb, nb = g.nb;
   ScanLaunch L;
   L.plan = v.dev;
   L.nrows = p->t->nrows;
@@ -1460,7 +1098,7 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                          tpb * kWordsPerTile * (int64_t)sizeof(uint64_t) <= kSinkLdsMaxBytes;
   L.sink_lds = sink_fits && (tu.sink_lds == 2 || (tu.sink_lds == 1 && tpb >= 128));
   L.ticket_groups = ticket_groups_of(c);
-  L.seg_counts = seg_counts;
+  L.seg_counts = o.seg_counts;
   L.words_wt = tu.scan_words_wt;
   L.int_range = 0;
   if (tu.scan_int_range && p->host.nterms >= 1) {
@@ -1493,33 +1131,28 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
   // plan with no float term (no NaN to report): no finalize at all -- its
   // ticket round trips are ~1 us at the end of every launch (10 M rows:
   // 10.7 -> 9.7 us, profiles/r03/fin)
-  if (!need_count && (mode == kModeBitmap || mode == kModeCount) && seg_counts && !p->host.has_real &&
+  if (!o.need_count && (mode == kModeBitmap || mode == kModeCount) && o.seg_counts && !p->host.has_real &&
       tu.fin_mode < 0)
     L.fin_mode = kFinSegOnly;
-  if (frame) {  // mbx_scan_count_frame_async: count_out is the frame
+  if (o.frame) {  // mbx_scan_count_frame_async: count_out is the frame
     L.fin_mode = kFinFrame;
     L.ticket = nullptr;
   }
   if (L.fin_mode == kFinSeparate) L.ticket = nullptr;
-  if (fused) {
+  if (o.fused) {
     int64_t* stamps = nullptr;
     if (c->tune.select_dbg & 8) {  // diagnostic stamps (mbx_diag_select_stamps)
       if (!c->stamps) HIPCHK(hipMalloc(&c->stamps, sizeof(int64_t) * 4 * kMaxStampBlocks));
       stamps = c->stamps;
     }
-    HIPCHK(launch_scan_select(L, c->lookback, p->t->row_offset, fused->ids, fused->total, c->stream, stamps,
+    HIPCHK(launch_scan_select(L, c->lookback, p->t->row_offset, o.fused->ids, o.fused->total, c->stream, stamps,
                               c->tune.select_dbg >> 4, c->tune.scan_select_waves, c->tune.select_flag_stride));
     return MBX_OK;
   }
-  if (form == kFormBits) {
-    L.bp = p->bits;
-    HIPCHK(launch_scan_bits(L, c->stream));
-  } else if (form == kFormBytes) {
-    L.sl = p->sliced;
-    HIPCHK(launch_scan_sliced(L, p->sliced_ncols, c->stream));
-  } else {
+  if (g.form != kFormColumns)
+    HIPCHK(launch_plane_scan(L, p, g.form, c->stream));
+  else
     HIPCHK(launch_scan(L, c->stream));
-  }
   if (L.fin_mode == kFinSeparate)
     HIPCHK(launch_finalize(parts, nb, L.agg_kind, agg_out, count_out, nan_out, c->stream));
   return MBX_OK;
@@ -1529,11 +1162,9 @@ static int scan_to_count(mbx_ctx* c, mbx_plan* p, int64_t* dev_count, int32_t* d
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  int64_t tpb, nb;
-  const int32_t form = count_geometry(c, p, *v, &tpb, &nb);
-  if ((rc = ensure_partials(c, nb))) return rc;
-  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_count, nullptr, dev_nan, nullptr, nullptr,
-                      true, false, form);
+  const ScanGeometry g = count_geometry(c, p, scan_tiles_per_block(c, p->t->nrows, *v));
+  if ((rc = ensure_partials(c, g.nb))) return rc;
+  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, g, dev_count, nullptr, dev_nan);
 }
 
 // NaN words: the *_async entry points report through dnan[0..1] ([1] sticky
@@ -1572,13 +1203,15 @@ int mbx::scan_count_parts(mbx_ctx* c, const mbx_plan* pc, int64_t* dev_parts, in
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  const int64_t tpb = scan_tiles_per_block(c, p->t->nrows, *v);
-  const int64_t nb = grid_blocks(p->t->nrows, tpb);
-  if (nb > cap) return fail(MBX_E_INVALID, "scan_count_parts: %lld blocks, capacity %lld", (long long)nb, (long long)cap);
-  if ((rc = ensure_partials(c, nb))) return rc;
-  *nparts = nb;
-  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, nullptr, nullptr, c->dnan, dev_parts, nullptr,
-                      false);
+  const ScanGeometry g = column_geometry(p, scan_tiles_per_block(c, p->t->nrows, *v));
+  if (g.nb > cap)
+    return fail(MBX_E_INVALID, "scan_count_parts: %lld blocks, capacity %lld", (long long)g.nb, (long long)cap);
+  if ((rc = ensure_partials(c, g.nb))) return rc;
+  *nparts = g.nb;
+  ScanOpts o;
+  o.seg_counts = dev_parts;
+  o.need_count = false;
+  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, g, nullptr, nullptr, c->dnan, o);
 }
 
 extern "C" int mbx_scan_count_async(mbx_ctx* c, const mbx_plan* pc, int64_t* dev_count) {
@@ -1604,14 +1237,14 @@ extern "C" int mbx_scan_count_frame_async(mbx_ctx* c, const mbx_plan* pc, int64_
   if (rc) return rc;
   PlanVariant* v = nullptr;
   if ((rc = plan_variant(p, -1, &v))) return rc;
-  int64_t tpb, nb;
-  const int32_t form = count_geometry(c, p, *v, &tpb, &nb);
-  if ((nb + kFrameSlots - 1) / kFrameSlots > kFrameMaxArrivalsPerSlot || p->t->nrows >= (int64_t(1) << 36))
+  const ScanGeometry g = count_geometry(c, p, scan_tiles_per_block(c, p->t->nrows, *v));
+  if ((g.nb + kFrameSlots - 1) / kFrameSlots > kFrameMaxArrivalsPerSlot || p->t->nrows >= (int64_t(1) << 36))
     return fail(MBX_E_INVALID, "scan_count_frame: %lld rows in %lld blocks do not fit a count frame",
-                (long long)p->t->nrows, (long long)nb);
-  if ((rc = ensure_partials(c, nb))) return rc;
-  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, tpb, dev_frame, nullptr, c->dnan, nullptr, nullptr,
-                      true, true, form);
+                (long long)p->t->nrows, (long long)g.nb);
+  if ((rc = ensure_partials(c, g.nb))) return rc;
+  ScanOpts o;
+  o.frame = true;
+  return enqueue_scan(c, p, *v, kModeCount, nullptr, c->partials, g, dev_frame, nullptr, c->dnan, o);
 }
 
 extern "C" int mbx_count_frame_fits(int64_t nblocks, int32_t nranks) {
@@ -1644,8 +1277,7 @@ extern "C" int mbx_scan_blocks(mbx_ctx* c, const mbx_plan* pc, int64_t* blocks) 
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  int64_t tpb;
-  count_geometry(c, p, *v, &tpb, blocks);
+  *blocks = count_geometry(c, p, scan_tiles_per_block(c, p->t->nrows, *v)).nb;
   return MBX_OK;
 }
 
@@ -1656,11 +1288,13 @@ static int scan_bitmap_into(mbx_ctx* c, mbx_plan* p, mbx_bitmap* b, int32_t* dev
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  const int64_t tpb = b->wpb / kWordsPerTile;
-  if (grid_blocks(p->t->nrows, tpb) != b->nseg) return fail(MBX_E_INVALID, "scan_bitmap: segment mismatch");
+  const ScanGeometry g = column_geometry(p, b->wpb / kWordsPerTile);
+  if (g.nb != b->nseg) return fail(MBX_E_INVALID, "scan_bitmap: segment mismatch");
   if ((rc = ensure_partials(c, b->nseg))) return rc;
-  return enqueue_scan(c, p, *v, kModeBitmap, b->words, c->partials, tpb, c->dcount, nullptr, dev_nan, b->segc,
-                      nullptr, need_count);
+  ScanOpts o;
+  o.seg_counts = b->segc;
+  o.need_count = need_count;
+  return enqueue_scan(c, p, *v, kModeBitmap, b->words, c->partials, g, c->dcount, nullptr, dev_nan, o);
 }
 
 // read back the count + NaN flag the last scan's final block wrote
@@ -1700,13 +1334,16 @@ static int scan_select_into(mbx_ctx* c, mbx_plan* p, mbx_bitmap* b, int64_t* dev
     PlanVariant* v = nullptr;
     int rc = plan_variant(p, -1, &v);
     if (rc) return rc;
-    const int64_t tpb = b->wpb / kWordsPerTile;
+    const ScanGeometry g = column_geometry(p, b->wpb / kWordsPerTile);
     if (c->tune.scan_ri != 0 && p->all_literal &&
-        scan_select_fusable(p->t->nrows, tpb, v->fast_k, v->fast_ks, p->host.nterms, p->host.has_real,
+        scan_select_fusable(p->t->nrows, g.tpb, v->fast_k, v->fast_ks, p->host.nterms, p->host.has_real,
                             c->tune.scan_select_waves) &&
-        grid_blocks(p->t->nrows, tpb) == b->nseg) {
+        g.nb == b->nseg) {
       const FusedSelect f{dev_ids, dev_count};
-      return enqueue_scan(c, p, *v, kModeBitmap, b->words, c->partials, tpb, dev_count, nullptr, dev_nan, b->segc, &f);
+      ScanOpts o;
+      o.seg_counts = b->segc;
+      o.fused = &f;
+      return enqueue_scan(c, p, *v, kModeBitmap, b->words, c->partials, g, dev_count, nullptr, dev_nan, o);
     }
   }
   int rc = scan_bitmap_into(c, p, b, dev_nan, false);
@@ -1809,10 +1446,9 @@ static int scan_agg(mbx_ctx* c, mbx_plan* p, int32_t agg_col, AggOut* dev_out, i
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, agg_col, &v);
   if (rc) return rc;
-  const int64_t tpb = scan_tiles_per_block(c, p->t->nrows, *v);
-  const int64_t nb = grid_blocks(p->t->nrows, tpb);
-  if ((rc = ensure_partials(c, nb))) return rc;
-  return enqueue_scan(c, p, *v, kModeAgg, nullptr, c->partials, tpb, nullptr, dev_out, dev_nan);
+  const ScanGeometry g = column_geometry(p, scan_tiles_per_block(c, p->t->nrows, *v));
+  if ((rc = ensure_partials(c, g.nb))) return rc;
+  return enqueue_scan(c, p, *v, kModeAgg, nullptr, c->partials, g, nullptr, dev_out, dev_nan);
 }
 
 extern "C" int mbx_scan_aggregate(mbx_ctx* c, const mbx_plan* pc, int32_t agg_col, mbx_agg* out) {

@@ -1,5 +1,5 @@
 // mbx_internal.hpp -- device-side plan layout and kernel launchers shared by
-// the C-ABI layer (mbx_api.cpp) and the CDNA4 kernels (mbx_kernels.hip).
+// the C-ABI layer (mbx_api.cpp, mbx_planes.cpp) and the CDNA4 kernels (mbx_*.hip).
 //
 // HBM layout (DESIGN.md "Data layout"):
 //   * int32 / float32 column: nrows contiguous 4-byte values, position order.
@@ -452,12 +452,25 @@ struct ProbeArgs {
 };
 hipError_t launch_read_probe(const ProbeArgs& A, hipStream_t s);
 
-int64_t grid_blocks(int64_t nrows, int64_t tiles_per_block);
+// blocks of a scan whose blocks own tiles_per_block wave tiles of tile_rows
+// rows (kTileRows, kSliceTileRows or kBitTileRows); an empty table takes one
+inline int64_t blocks_for(int64_t nrows, int64_t tile_rows, int64_t tiles_per_block) {
+  const int64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
+  const int64_t g = (ntiles + tiles_per_block - 1) / tiles_per_block;
+  return g < 1 ? 1 : g;
+}
+// nrows rounded up to whole tiles, at least one (the row stride of a plane)
+inline int64_t padded_rows(int64_t nrows, int64_t tile_rows) {
+  const int64_t tiles = (nrows + tile_rows - 1) / tile_rows;
+  return (tiles < 1 ? 1 : tiles) * tile_rows;
+}
+inline int64_t grid_blocks(int64_t nrows, int64_t tiles_per_block) {
+  return blocks_for(nrows, kTileRows, tiles_per_block);
+}
 int64_t choose_tiles_per_block(int64_t nrows);
 
 hipError_t launch_scan(const ScanLaunch& L, hipStream_t s);
 // sliced COUNT scan: L.sl set, L.tiles_per_block in sliced tiles, ncols = the plan's column slots
-int64_t sliced_grid_blocks(int64_t nrows, int64_t tiles_per_block);
 hipError_t launch_scan_sliced(const ScanLaunch& L, int32_t ncols, hipStream_t s);
 // key min / max of an int32 column into mm[0..1] (mm preset to ~0u, 0u)
 hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, hipStream_t s);
@@ -466,7 +479,6 @@ hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, 
 hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, int64_t pstride, uint8_t* out,
                               hipStream_t s);
 // bit-plane COUNT scan: L.bp set, L.tiles_per_block in bit tiles
-int64_t bits_grid_blocks(int64_t nrows, int64_t tiles_per_block);
 hipError_t launch_scan_bits(const ScanLaunch& L, hipStream_t s);
 // planes 0..w-1 (bits h..h-w+1 of key - base) of the column into out, plane j at
 // out + j * pstride dwords; pstride = rows padded to a whole bit tile / 32, the padding written as 0

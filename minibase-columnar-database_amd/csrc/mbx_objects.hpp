@@ -145,6 +145,26 @@ struct mbx_table {
   bool aligned16 = true;
 };
 
+// how COUNT launches of a plan read the table (mbx_plan_slice_form)
+enum SliceForm : int32_t { kFormColumns = 0, kFormBytes = 1, kFormBits = 2 };
+
+// A plan's COUNT scans bound to planes of its table's columns (mbx_planes.cpp).
+// It holds while gen is the table's slice_gen; a plan bound to an older
+// generation, or never bound (kFormColumns), scans the columns.
+struct PlaneBinding {
+  int32_t form = kFormColumns;
+  void* dev = nullptr;  // device KSlicePlan (kFormBytes: k_scan_sliced) / KBitPlan (kFormBits: k_scan_bits)
+  int32_t n = 0;        // kFormBytes: the plan's column slots; kFormBits: the planes it reads per tile
+  uint64_t gen = 0;
+};
+
+// segment size and grid of one scan launch: tpb tiles per block -- 256-row
+// tiles for kFormColumns, sliced tiles for kFormBytes, bit tiles for kFormBits
+struct ScanGeometry {
+  int32_t form;
+  int64_t tpb, nb;
+};
+
 struct PlanVariant {
   int32_t agg_col = -1;  // -1: filter only
   KPlan* dev = nullptr;
@@ -161,15 +181,7 @@ struct mbx_plan {
   bool all_literal = true;        // every term is `column OP literal`
   bool str_lit_fits16 = true;     // every string literal is <= 16 bytes
   std::deque<PlanVariant> variants;
-  // sliced COUNT scan (k_scan_sliced): the device plan over the table's slices
-  // of generation slice_gen; null: COUNT scans read the columns
-  mbx::KSlicePlan* sliced = nullptr;
-  int32_t sliced_ncols = 0;
-  uint64_t slice_gen = 0;
-  // bit-plane COUNT scan (k_scan_bits) instead: the device plan over the
-  // slices' bit planes (sliced is then null), and the planes it reads per tile
-  mbx::KBitPlan* bits = nullptr;
-  int32_t bits_planes = 0;
+  PlaneBinding planes;  // set by mbx::bind_planes; dev is owned
 };
 
 struct mbx_bitmap {
@@ -241,6 +253,13 @@ int bitmap_recount(mbx_ctx* c, mbx_bitmap* b);
 // term (its NaN needs the finalize) or more blocks than cap
 int scan_count_parts(mbx_ctx* c, const mbx_plan* p, int64_t* dev_parts, int64_t cap, int64_t* nparts);
 bool plan_has_real(const mbx_plan* p);
+// mbx_planes.cpp.  bind_planes: mbx_plan_compile's last step -- binds the COUNT
+// scans of a slice-eligible plan to its columns' planes (building missing ones);
+// count_geometry: the plan's COUNT launch, given the column scan's tpb;
+// launch_plane_scan: that launch for g.form != kFormColumns (sets L.sl / L.bp)
+void bind_planes(mbx_ctx* c, mbx_plan* p);
+ScanGeometry count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tpb);
+hipError_t launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s);
 // mbx_comm.cpp: mbx_sync / mbx_free of a context with a communicator
 int comm_sync(mbx_ctx* c);
 void comm_release_of(mbx_ctx* c);

@@ -259,6 +259,11 @@ int mbx_plan_sliced(mbx_ctx *ctx, const mbx_plan *p, int32_t *sliced);
 /* *form = what COUNT launches of this plan currently read: 0 the columns,
  * 1 byte planes, 2 bit planes (mbx_plan_sliced reports 1 for both 1 and 2) */
 int mbx_plan_slice_form(mbx_ctx *ctx, const mbx_plan *p, int32_t *form);
+/* *shallow = 1 when COUNT launches of this plan currently take the shallow
+ * bit-plane kernel (k_scan_bits1): form 2, every bound of every term decided
+ * on its column's top kept bit (mbx_bitslice_bound: *depth <= 1), and the
+ * tuning knob bits_shallow (default 1) not 0; else 0.  The form is 2 either way. */
+int mbx_plan_bit_shallow(mbx_ctx *ctx, const mbx_plan *p, int32_t *shallow);
 
 /* ---- ColumnarFileScan (R/iterator/ColumnarFileScan.java:156-188) --------- */
 /* COUNT of get_next() results: Query.executeFileScan's resultCount. */
@@ -509,7 +514,8 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * "join_plain", "join_chunk_words" (pair-matrix words per chunk of mbx_join, 1 .. 2^24; anything else: 2^24),
  * "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
- * "comm_same_stream", "scan_words_wt", "auto_slice", "auto_bitslice" (mbx_plan_compile above), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
+ * "comm_same_stream", "scan_words_wt", "auto_slice", "auto_bitslice" (mbx_plan_compile above),
+ * "bits_shallow" (0: every bit-plane plan takes k_scan_bits; read at launch), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,
  * 2 write-through, 3 nontemporal); "reset" restores the defaults. */
 int mbx_set_tuning(mbx_ctx *ctx, const char *knob, int64_t value);

@@ -109,6 +109,7 @@ static void tuning_defaults(MbxTuning& t) {
   t.comm_same_stream = (int32_t)env_knob("MBX_COMM_SAME_STREAM", 1);
   t.auto_slice = env_knob("MBX_AUTO_SLICE", 1) != 0;
   t.auto_bitslice = env_knob("MBX_AUTO_BITSLICE", 1) != 0;
+  t.bits_shallow = env_knob("MBX_BITS_SHALLOW", 1) != 0;
   t.cnf_blocks = (int32_t)env_knob("MBX_CNF_BLOCKS", 0);
   t.cnf_flag_stride = env_knob("MBX_CNF_FLAG_STRIDE", 1) == kFlagStride ? kFlagStride : 1;
   t.cnf_lookback = (int32_t)env_knob("MBX_CNF_LOOKBACK", 0);
@@ -342,6 +343,7 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
   else if (!strcmp(knob, "comm_same_stream")) t.comm_same_stream = v != 0;
   else if (!strcmp(knob, "auto_slice")) t.auto_slice = v != 0;
   else if (!strcmp(knob, "auto_bitslice")) t.auto_bitslice = v != 0;
+  else if (!strcmp(knob, "bits_shallow")) t.bits_shallow = v != 0;
   else return fail(MBX_E_INVALID, "mbx_set_tuning: unknown knob `%s`", knob);
   return MBX_OK;
 }

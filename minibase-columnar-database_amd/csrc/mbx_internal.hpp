@@ -275,6 +275,15 @@ inline uint32_t bit_term_meta(int32_t neg, int32_t slo, int32_t shi, int32_t dlo
          ((uint32_t)dhi << 9);
 }
 
+// bit_term_meta's fields, for the kernels and the host
+__host__ __device__ inline bool bit_neg(uint32_t m) { return m & 1u; }
+__host__ __device__ inline int32_t bit_slo(uint32_t m) { return (int32_t)((m >> 1) & 3u); }
+__host__ __device__ inline int32_t bit_shi(uint32_t m) { return (int32_t)((m >> 3) & 3u); }
+__host__ __device__ inline int bit_dlo(uint32_t m) { return (int)((m >> 5) & 15u); }
+__host__ __device__ inline int bit_dhi(uint32_t m) { return (int)((m >> 9) & 15u); }
+// the planes a term reads
+__host__ __device__ inline int bit_term_depth(uint32_t m) { return bit_dlo(m) > bit_dhi(m) ? bit_dlo(m) : bit_dhi(m); }
+
 struct KBitPlan {
   int32_t nterms;
   int32_t nconj, never;                  // as KSlicePlan
@@ -283,6 +292,18 @@ struct KBitPlan {
   int64_t pstride;                       // dwords between planes (rows padded to a whole bit tile)
   KBitTerm terms[kSliceMaxTerms];
 };
+// every term decided on its column's top kept bit: the plan can take k_scan_bits1
+inline bool bit_plan_shallow(const KBitPlan& b) {
+  for (int32_t i = 0; i < b.nterms; i++)
+    if (bit_term_depth(b.terms[i].meta) > 1) return false;
+  return true;
+}
+// the terms that read a plane (a shallow plan's loads per tile)
+inline int32_t bit_plan_reads(const KBitPlan& b) {
+  int32_t n = 0;
+  for (int32_t i = 0; i < b.nterms; i++) n += bit_term_depth(b.terms[i].meta) > 0;
+  return n;
+}
 
 // dynamic LDS per block for the staged BitSet (4 blocks per CU: <= 128 KB of
 // the CU's 160 KB)
@@ -478,8 +499,10 @@ hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, 
 // pstride = rows padded to a whole sliced tile, the padding written as 0)
 hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, int64_t pstride, uint8_t* out,
                               hipStream_t s);
-// bit-plane COUNT scan: L.bp set, L.tiles_per_block in bit tiles
-hipError_t launch_scan_bits(const ScanLaunch& L, hipStream_t s);
+// bit-plane COUNT scan: L.bp set, L.tiles_per_block in bit tiles.  shallow: the host copy of a plan
+// with bit_plan_shallow (its launch is k_scan_bits1, which takes what it needs of the plan in its
+// kernel arguments), or null (k_scan_bits, which reads L.bp)
+hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s);
 // planes 0..w-1 (bits h..h-w+1 of key - base) of the column into out, plane j at
 // out + j * pstride dwords; pstride = rows padded to a whole bit tile / 32, the padding written as 0
 hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,

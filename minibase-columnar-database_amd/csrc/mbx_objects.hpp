@@ -75,6 +75,8 @@ struct MbxTuning {
                                   // slice-eligible plan and binds its COUNT scans to them (0: plans read the columns)
   int32_t auto_bitslice = 1;      // MBX_AUTO_BITSLICE: a sliced plan whose every bound is decided within its column's
                                   // bit planes binds to those (k_scan_bits); 0: every sliced plan takes the byte planes
+  int32_t bits_shallow = 1;       // MBX_BITS_SHALLOW: a bit-plane plan whose every term has depth <= 1 takes
+                                  // k_scan_bits1 (read at launch); 0: every bit-plane plan takes k_scan_bits
   int32_t select_dbg = 0;         // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
                                   // instead of the chained look-back, 512 write-through flip; -DMBX_DIAG
                                   // builds only: k_select_ids bit 0 no prefix / bit 1 no emission, the
@@ -156,6 +158,7 @@ struct PlaneBinding {
   void* dev = nullptr;  // device KSlicePlan (kFormBytes: k_scan_sliced) / KBitPlan (kFormBits: k_scan_bits)
   int32_t n = 0;        // kFormBytes: the plan's column slots; kFormBits: the planes it reads per tile
   uint64_t gen = 0;
+  mbx::KBitPlan bits{};  // kFormBits: the host copy of *dev (the shallow kernel's arguments are made from it)
 };
 
 // segment size and grid of one scan launch: tpb tiles per block -- 256-row

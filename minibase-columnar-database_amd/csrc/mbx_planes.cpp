@@ -268,7 +268,9 @@ static bool bind_bits(mbx_ctx* c, mbx_plan* p) {
     bp.terms[i].planes = t->slices[(size_t)col].bdev;
   }
   slice_conjuncts(h, bp.cmask, &bp.nconj, &bp.never);
-  return upload_binding(p, kFormBits, &bp, sizeof(bp), planes);
+  if (!upload_binding(p, kFormBits, &bp, sizeof(bp), planes)) return false;
+  p->planes.bits = bp;  // k_scan_bits1's kernel arguments are made from the host copy at each launch
+  return true;
 }
 
 // Builds the missing slices of the plan's columns and binds the plan's COUNT
@@ -358,10 +360,15 @@ ScanGeometry mbx::count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tp
   return ScanGeometry{form, tpb, blocks_for(nrows, tile_rows, tpb)};
 }
 
+// a bit-plane plan's launch is the shallow kernel's (mbx_plan_bit_shallow)
+static bool takes_shallow(const mbx_plan* p) {
+  return p->ctx->tune.bits_shallow != 0 && bit_plan_shallow(p->planes.bits);
+}
+
 hipError_t mbx::launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s) {
   if (form == kFormBits) {
     L.bp = (const KBitPlan*)p->planes.dev;
-    return launch_scan_bits(L, s);
+    return launch_scan_bits(L, takes_shallow(p) ? &p->planes.bits : nullptr, s);
   }
   L.sl = (const KSlicePlan*)p->planes.dev;
   return launch_scan_sliced(L, p->planes.n, s);
@@ -380,5 +387,13 @@ extern "C" int mbx_plan_slice_form(mbx_ctx* c, const mbx_plan* p, int32_t* form)
   NOTNULL(p);
   NOTNULL(form);
   *form = plan_form_now(p);
+  return MBX_OK;
+}
+
+extern "C" int mbx_plan_bit_shallow(mbx_ctx* c, const mbx_plan* p, int32_t* shallow) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(shallow);
+  *shallow = plan_form_now(p) == kFormBits && takes_shallow(p) ? 1 : 0;
   return MBX_OK;
 }

@@ -1,8 +1,10 @@
 // mbx_planes.hip -- COUNT scans over byte planes (k_scan_sliced) and bit
-// planes (k_scan_bits, BitWeaving/V) of int32 columns, and the kernels that
+// planes (k_scan_bits, k_scan_bits1, BitWeaving/V) of int32 columns, and the kernels that
 // build the planes.  The scans answer what ColumnarFileScan.get_next
 // (R/iterator/ColumnarFileScan.java:156-172) counts, reading only the bytes
 // or bits of each row that decide the predicate.
+#include <type_traits>
+
 #include "mbx_device.hpp"
 
 namespace mbx {
@@ -305,28 +307,31 @@ __global__ __launch_bounds__(kBlock) void k_slice_build(const int32_t* __restric
 // the next plane in flight while the current one is compared.  A bound keeps
 // `ok` (rows that already hold it) and `eq` (rows equal to it so far) as
 // 128-bit row masks; its bits and depth are scalars and a step is branch-free.
-__device__ __forceinline__ bool bit_neg(uint32_t m) { return m & 1u; }
-__device__ __forceinline__ int32_t bit_slo(uint32_t m) { return (int32_t)((m >> 1) & 3u); }
-__device__ __forceinline__ int32_t bit_shi(uint32_t m) { return (int32_t)((m >> 3) & 3u); }
-__device__ __forceinline__ int bit_dlo(uint32_t m) { return (int)((m >> 5) & 15u); }
-__device__ __forceinline__ int bit_dhi(uint32_t m) { return (int)((m >> 9) & 15u); }
-
-__device__ __forceinline__ v4u bit_splat(uint32_t f) {
-  v4u v = {f, f, f, f};
-  return v;
+// The term and conjunct rules below are written once over the row-mask type V:
+// v4u in the kernels (a lane's 128 rows of a tile), uint32_t where the host
+// works a shallow plan's truth table out before the launch (bits1_plan_of).
+// (bit_neg .. bit_dhi, the fields of a term's meta word: mbx_internal.hpp)
+template <class V = v4u>
+__host__ __device__ __forceinline__ V bit_splat(uint32_t f) {
+  if constexpr (std::is_same<V, uint32_t>::value) {
+    return f;
+  } else {
+    V v = {f, f, f, f};
+    return v;
+  }
 }
 
 // plane j (x) against bit j of the bound `k >= bits` (UPPER: `k <= bits`) of
 // depth d.  y: the rows beyond the bound on this bit, were the bound's bit the
 // other value -- a lower bound's 1 / an upper bound's 0 lets only equal rows
 // go on (n = 0), the other value also passes the rows beyond it (n = ~0).
-template <bool UPPER>
-__device__ __forceinline__ void bit_step(v4u& ok, v4u& eq, const v4u& x, uint32_t bits, int j, int d) {
+template <bool UPPER, class V>
+__host__ __device__ __forceinline__ void bit_step(V& ok, V& eq, const V& x, uint32_t bits, int j, int d) {
   const uint32_t a = j < d ? ~0u : 0u;
   const uint32_t n = (((bits >> j) & 1u) != (UPPER ? 1u : 0u)) ? 0u : ~0u;
-  const v4u y = UPPER ? ~x : x;
-  ok |= eq & y & bit_splat(n & a);
-  eq &= (y ^ bit_splat(n)) | bit_splat(~a);
+  const V y = UPPER ? ~x : x;
+  ok |= eq & y & bit_splat<V>(n & a);
+  eq &= (y ^ bit_splat<V>(n)) | bit_splat<V>(~a);
 }
 
 __device__ __forceinline__ uint32_t bit_popc(const v4u& v) {
@@ -339,6 +344,31 @@ struct BitTerms {
   int nterms;
   int64_t pstride;
 };
+
+// The rows every required conjunct selects, given each term's rows
+template <class V>
+__host__ __device__ __forceinline__ V bit_cnf(const SliceCnf& cn, const V (&r)[kSliceMaxTerms]) {
+  V a = bit_splat<V>(cn.never ? 0u : ~0u);
+#pragma unroll
+  for (int q = 0; q < kSliceMaxTerms; ++q)
+    if (q < cn.nconj) {
+      V o = bit_splat<V>(0u);
+#pragma unroll
+      for (int ti = 0; ti < kSliceMaxTerms; ++ti)
+        if ((cn.cmask[q] >> ti) & 1u) o |= r[ti];
+      a &= o;
+    }
+  return a;
+}
+
+__host__ __device__ __forceinline__ SliceCnf bit_cnf_of(const KBitPlan& B) {
+  SliceCnf cn;
+  cn.nconj = B.nconj;
+  cn.never = B.never;
+#pragma unroll
+  for (int q = 0; q < kSliceMaxTerms; ++q) cn.cmask[q] = B.cmask[q];
+  return cn;
+}
 
 // The selected rows of U tiles; dw[u]: the lane's first dword of tile u in every plane
 template <int U>
@@ -390,6 +420,8 @@ __device__ __forceinline__ void bits_eval(const BitTerms& T, const SliceCnf& cn,
         r[ti][u] = bit_neg(m) ? ~v : v;
       }
     }
+  // bit_cnf's rule, written out over the tiles: going through bit_cnf's per-tile copy of
+  // r changed this kernel's register allocation and cost it 4 % at 100 M rows
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     v4u a = bit_splat(cn.never ? 0u : ~0u);
@@ -404,6 +436,17 @@ __device__ __forceinline__ void bits_eval(const BitTerms& T, const SliceCnf& cn,
       }
     res[u] = a;
   }
+}
+
+// a lane's selected rows -> the wave's count -> the block's arrival
+__device__ __forceinline__ void bits_finish(uint32_t cnt, int lane, const ScanLaunch& L) {
+  uint64_t wc = cnt;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) wc += __shfl_xor(wc, m);
+  Acc acc;
+  acc_init(acc);
+  acc.count = lane == 0 ? (int64_t)wc : 0;
+  block_reduce_store<false>(acc, L);
 }
 
 // U tiles in flight per wave; a block owns a contiguous segment of bit tiles
@@ -430,11 +473,7 @@ __global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
     T.hi[ti] = B->terms[ti].hi;
     T.meta[ti] = B->terms[ti].meta;
   }
-  SliceCnf cn;
-  cn.nconj = B->nconj;
-  cn.never = B->never;
-#pragma unroll
-  for (int q = 0; q < kSliceMaxTerms; ++q) cn.cmask[q] = B->cmask[q];
+  const SliceCnf cn = bit_cnf_of(*B);
   constexpr int kTileDwords = kBitTileRows / 32;
   gu32* del = (gu32*)L.deleted;
   const bool del16 = DEL && (reinterpret_cast<uintptr_t>(L.deleted) & 15) == 0;  // uniform
@@ -477,13 +516,192 @@ __global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
     bits_eval<1>(T, cn, dw, res);
     cnt += bit_popc(res[0] & live);
   }
-  uint64_t wc = cnt;
+  bits_finish(cnt, lane, L);
+}
+
+// ------------------------------------------- shallow bit-plane COUNT scan
+//
+// A plan whose every bound is decided on its column's top kept bit (depth <= 1:
+// C3, any bound that is round at that bit, two-key columns) reads at most one
+// plane per term, NP per tile, and needs none of k_scan_bits' per-bound state:
+// its predicate is a bitwise function of the tile's NP dwords.  The host works
+// that function out before the launch (bits1_plan_of: the term and conjunct
+// rules above over probe words) and the kernel arguments carry its 2^NP-row
+// truth table and the NP plane pointers, nothing else of the plan.  A tile then
+// costs one select per table node, and what is left per lane is the loads: a
+// wave issues all of a batch's -- kB tiles x (NP planes + the deleted image), 12
+// sixteen-byte loads per lane where that divides -- before it waits for the
+// first: one round trip for a C3 segment.  A tile's address is scalar (only the
+// lane offset is a register), so the 48 load registers fit 64 VGPRs, 8 waves
+// per SIMD.
+// Four planes keep 8 loads per lane live (10 with the deleted image): the third
+// tile's 4 would spill beside the 8 partial results of a four-plane table.
+constexpr int bits1_batch(int np, bool del) {
+  return np >= 4 ? 2 : 12 / (np + (del ? 1 : 0) > 0 ? np + (del ? 1 : 0) : 1);
+}
+
+struct Bits1Plan {
+  const uint32_t* pl[kSliceMaxTerms];  // slot k: plane 0 of the k-th term that reads one
+  uint32_t table;                      // bit i: rows whose plane-k bit is bit k of i are selected
+  uint32_t pad_;
+};
+
+// A term of depth <= 1 over plane 0 of its column (x: any value at depth 0)
+template <class V>
+__host__ __device__ __forceinline__ V bit_term1(uint32_t m, uint32_t lo, uint32_t hi, const V& x) {
+  V lok = bit_splat<V>(bit_slo(m) == kSliceHolds ? ~0u : 0u), leq = bit_splat<V>(bit_slo(m) == kSliceEqual ? ~0u : 0u);
+  V hok = bit_splat<V>(bit_shi(m) == kSliceHolds ? ~0u : 0u), heq = bit_splat<V>(bit_shi(m) == kSliceEqual ? ~0u : 0u);
+  bit_step<false>(lok, leq, x, lo, 0, bit_dlo(m));
+  bit_step<true>(hok, heq, x, hi, 0, bit_dhi(m));
+  const V v = (lok | leq) & (hok | heq);
+  return bit_neg(m) ? ~v : v;
+}
+
+// Plane slots and truth table of a shallow plan: the predicate over probe
+// words, plane k's probe holding bit k of every index 0..15
+static Bits1Plan bits1_plan_of(const KBitPlan& B) {
+  constexpr uint32_t kProbe[kSliceMaxTerms] = {0xAAAAu, 0xCCCCu, 0xF0F0u, 0xFF00u};
+  Bits1Plan P{};
+  uint32_t r[kSliceMaxTerms] = {0u, 0u, 0u, 0u};
+  int slot = 0;
+  for (int ti = 0; ti < B.nterms; ++ti) {
+    const KBitTerm& t = B.terms[ti];
+    uint32_t probe = 0u;
+    if (bit_term_depth(t.meta) > 0) {
+      P.pl[slot] = t.planes;
+      probe = kProbe[slot++];
+    }
+    r[ti] = bit_term1<uint32_t>(t.meta, t.lo, t.hi, probe);
+  }
+  P.table = bit_cnf(bit_cnf_of(B), r) & 0xFFFFu;
+  return P;
+}
+
+// The selected rows of one dword of NP planes.  Shannon expansion of the truth
+// table: for each value c of planes 1.. the rows are (x[0] & la[c]) ^ lb[c]
+// (plane 0, its complement or a constant); plane k then picks between the two
+// halves that differ in its bit.
+template <int NP>
+__device__ __forceinline__ uint32_t bits1_rows(const uint32_t (&x)[NP > 0 ? NP : 1],
+                                               const uint32_t (&la)[1 << (NP > 0 ? NP - 1 : 0)],
+                                               const uint32_t (&lb)[1 << (NP > 0 ? NP - 1 : 0)]) {
+  constexpr int kC = 1 << (NP > 0 ? NP - 1 : 0);
+  uint32_t g[kC];
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) wc += __shfl_xor(wc, m);
-  Acc acc;
-  acc_init(acc);
-  acc.count = lane == 0 ? (int64_t)wc : 0;
-  block_reduce_store<false>(acc, L);
+  for (int c = 0; c < kC; ++c) g[c] = (x[0] & la[c]) ^ lb[c];
+#pragma unroll
+  for (int k = 1; k < NP; ++k)
+#pragma unroll
+    for (int c = 0; c < (kC >> k); ++c) g[c] = (x[k] & g[2 * c + 1]) | (~x[k] & g[2 * c]);
+  return g[0];
+}
+
+// The address of a lane's 16 bytes of the tile that starts at the uniform
+// address p, as scalar base + 32-bit lane offset: one VGPR per address instead
+// of two.  Both halves pass through an empty asm the optimizer cannot look
+// through -- left alone, hipcc hoists the widened lane offset (or base + lane
+// offset) out of the tile loop as a 64-bit vector value and every load pays a
+// 64-bit vector add and a register pair.
+__device__ __forceinline__ const char* bit_tile_lane(const uint32_t* p, int lane) {
+  uint64_t a = reinterpret_cast<uint64_t>(p);
+  uint32_t off = (uint32_t)lane * 16u;
+  asm("" : "+s"(a));
+  asm("" : "+v"(off));
+  return reinterpret_cast<const char*>(a) + off;
+}
+__device__ __forceinline__ v4u bit_tile_load(const uint32_t* p, int lane) {
+  return __builtin_nontemporal_load((gv4u*)bit_tile_lane(p, lane));
+}
+
+// Segments, tile ownership, the partial tile and the deleted image as in
+// k_scan_bits; kB tiles per batch instead of U.
+template <int NP, bool DEL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_bits1(ScanLaunch L,
+                                                                                                  Bits1Plan P) {
+  constexpr int kB = bits1_batch(NP, DEL);
+  constexpr int kNP = NP > 0 ? NP : 1, kC = 1 << (kNP - 1);
+  constexpr int kTileDwords = kBitTileRows / 32;
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)uniform(threadIdx.x >> 6);
+  const int64_t nrows = L.nrows;
+  const int64_t ntiles = (nrows + kBitTileRows - 1) / kBitTileRows;
+  const int64_t t0 = (int64_t)blockIdx.x * L.tiles_per_block;
+  const int64_t t1 = min(t0 + L.tiles_per_block, ntiles);
+  const uint32_t* pl[kNP];
+#pragma unroll
+  for (int k = 0; k < kNP; ++k) pl[k] = P.pl[k];
+  uint32_t la[kC], lb[kC];  // uniform: bits1_rows' leaves
+#pragma unroll
+  for (int c = 0; c < kC; ++c) {
+    const uint32_t f0 = (P.table >> (2 * c)) & 1u, f1 = (P.table >> (2 * c + 1)) & 1u;
+    lb[c] = f0 ? ~0u : 0u;
+    la[c] = f0 != f1 ? ~0u : 0u;
+  }
+  gu32* del = (gu32*)L.deleted;
+  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(L.deleted) & 15) == 0;  // uniform
+
+  uint32_t cnt = 0;
+  // full tiles in the main loop; tile numbers fit 32 bits (rows < 2^40), which keeps the loop's compares scalar
+  const int tf = (int)min(t1, nrows / kBitTileRows);
+  for (int base = (int)min(t0 + wave, (int64_t)tf); base < tf; base += kWaves * kB) {
+    v4u x[kB][kNP], dead[kB];
+    // every load of the batch, unconditional; a tile past the full tiles is the last one again, and is not counted
+    int64_t dw[kB];  // the tile's first dword in every plane (uniform)
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+      dw[u] = (int64_t)min(base + u * kWaves, tf - 1) * kTileDwords;
+      x[u][0] = bit_splat(0u);
+#pragma unroll
+      for (int k = 0; k < NP; ++k) x[u][k] = bit_tile_load(pl[k] + dw[u], lane);
+    }
+    if (DEL) {
+      if (del16) {
+#pragma unroll
+        for (int u = 0; u < kB; ++u) dead[u] = bit_tile_load(reinterpret_cast<const uint32_t*>(L.deleted) + dw[u], lane);
+      } else {
+#pragma unroll
+        for (int u = 0; u < kB; ++u) {
+          gu32* d = (gu32*)bit_tile_lane(reinterpret_cast<const uint32_t*>(L.deleted) + dw[u], lane);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dead[u][i] = d[i];
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // no use of a loaded tile is scheduled among the loads: one wait, after the last
+
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+      uint32_t c = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        uint32_t xi[kNP];
+#pragma unroll
+        for (int k = 0; k < kNP; ++k) xi[k] = x[u][k][i];
+        const uint32_t rows = bits1_rows<NP>(xi, la, lb);
+        c += (uint32_t)__popc(DEL ? rows & ~dead[u][i] : rows);
+      }
+      cnt += base + u * kWaves < tf ? c : 0u;
+    }
+  }
+  const int64_t tp = nrows / kBitTileRows;  // the partial tile, owned like any other tile of [t0, t1)
+  if ((nrows % kBitTileRows) != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
+    v4u xp[kNP];
+    xp[0] = bit_splat(0u);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) xp[k] = bit_tile_load(pl[k] + tp * kTileDwords, lane);
+    const int64_t dw = tp * kTileDwords + lane * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t rem = nrows - (dw + i) * 32;  // the dword's rows below nrows
+      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << (int)rem) - 1u));
+      if (DEL && rem > 0) valid &= ~del[dw + i];
+      uint32_t xi[kNP];
+#pragma unroll
+      for (int k = 0; k < kNP; ++k) xi[k] = xp[k][i];
+      cnt += (uint32_t)__popc(bits1_rows<NP>(xi, la, lb) & valid);
+    }
+  }
+  bits_finish(cnt, lane, L);
 }
 
 // planes 0..w-1 of 64 rows per wave step: one ballot per plane, lane j stores
@@ -512,12 +730,33 @@ __global__ __launch_bounds__(kBlock) void k_bitslice_build(const int32_t* __rest
 #ifndef MBX_BITS_U
 #define MBX_BITS_U 2
 #endif
-hipError_t launch_scan_bits(const ScanLaunch& L, hipStream_t s) {
-  const dim3 grid((unsigned)blocks_for(L.nrows, kBitTileRows, L.tiles_per_block));
+template <int NP>
+static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
+  const Bits1Plan P = bits1_plan_of(B);
   if (L.deleted)
-    hipLaunchKernelGGL((k_scan_bits<true, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+    hipLaunchKernelGGL((k_scan_bits1<NP, true>), grid, dim3(kBlock), 0, s, L, P);
   else
-    hipLaunchKernelGGL((k_scan_bits<false, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+    hipLaunchKernelGGL((k_scan_bits1<NP, false>), grid, dim3(kBlock), 0, s, L, P);
+}
+
+hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s) {
+  const dim3 grid((unsigned)blocks_for(L.nrows, kBitTileRows, L.tiles_per_block));
+  if (!shallow) {
+    if (L.deleted)
+      hipLaunchKernelGGL((k_scan_bits<true, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+    else
+      hipLaunchKernelGGL((k_scan_bits<false, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+    return hipGetLastError();
+  }
+  if (!bit_plan_shallow(*shallow)) return hipErrorInvalidValue;
+  switch (bit_plan_reads(*shallow)) {  // one plane per term that reads
+    case 0: bits1_launch<0>(L, *shallow, grid, s); break;
+    case 1: bits1_launch<1>(L, *shallow, grid, s); break;
+    case 2: bits1_launch<2>(L, *shallow, grid, s); break;
+    case 3: bits1_launch<3>(L, *shallow, grid, s); break;
+    case 4: bits1_launch<4>(L, *shallow, grid, s); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

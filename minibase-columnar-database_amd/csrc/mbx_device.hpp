@@ -304,10 +304,10 @@ __device__ __forceinline__ bool packed_arrive(uint64_t* w, uint64_t add, uint32_
   return true;
 }
 
-// true for the final arriver of the launch
+// true for the final arriver of the launch; nb: the grid's blocks
 __device__ __forceinline__ bool packed_count_finalize(uint32_t* ticket, int groups, int64_t count, int nan,
-                                                      int64_t* count_out, int32_t* nan_out) {
-  const uint32_t nb = gridDim.x;
+                                                      int64_t* count_out, int32_t* nan_out,
+                                                      const uint32_t nb = gridDim.x) {
   uint64_t add = pack_count(count, nan ? 1u : 0u), sum;
   if (groups > 1 && nb > (uint32_t)groups) {
     const uint32_t G = (uint32_t)groups;
@@ -439,6 +439,72 @@ __device__ __forceinline__ void block_reduce_store(Acc a, const ScanLaunch& L) {
 #endif
     finalize_block<true, !FULL>(L.partials, gridDim.x, L.agg_kind, L.agg_out, L.count_out, L.nan_out);
   }
+}
+
+// ---- COUNT epilogue of the plane scans (mbx_planes.hip)
+//
+// A plane kernel's body is one or two round trips to memory, so what follows
+// its last load is on the critical path of every block.  An integer COUNT needs
+// none of Acc but the count: the wave's sum stays in registers (DPP), a wave
+// hands one 64-bit word to LDS, and thread 0 adds four of them.
+
+// The wave's sum of v (every lane's v < 2^26, so no carry is lost), uniform.
+// row_shr 1, 2, 4, 8 leave each row of 16 lanes' prefix sums, row_bcast:15 adds
+// rows 0 / 2's totals to rows 1 / 3, row_bcast:31 adds lane 31's to rows 2 and
+// 3: lane 63 holds the total.  Lanes a step does not write add `old` = 0.
+__device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The wave's row count from each lane's, exact for any 32-bit lane counts: the
+// two 16-bit halves are summed on their own (64 lanes x 2^16 < 2^22 each)
+__device__ __forceinline__ uint64_t wave_count(uint32_t cnt) {
+  const uint32_t lo = wave_sum_dpp(cnt & 0xffffu), hi = wave_sum_dpp(cnt >> 16);
+  return (uint64_t)lo + ((uint64_t)hi << 16);
+}
+
+// How a plane kernel's block hands its count on: a compile-time choice made on
+// the host (plane_fin_of), so the two hot forms carry no other form's code
+enum PlaneFin : int {
+  kPlaneFinGeneral = 0,  // block_reduce_store: every FinMode, seg_counts
+  kPlaneFinPacked = 1,   // kFinPackedCount with a ticket: packed_count_finalize
+  kPlaneFinFrame = 2,    // kFinFrame: a no-return add into the count frame
+};
+
+// kPlaneFinPacked / kPlaneFinFrame; out: the launch's count word / its count
+// frame.  An integer plan sees no NaN: the packed words carry none.
+template <int FIN>
+__device__ __forceinline__ void plane_count_finish(uint32_t cnt, int64_t* out, uint32_t* ticket, int groups,
+                                                   int32_t* nan_out, const uint32_t nb = gridDim.x) {
+  static_assert(FIN == kPlaneFinPacked || FIN == kPlaneFinFrame, "the general form is plane_count_general");
+  __shared__ uint64_t wsum[kWaves];
+  const uint64_t wc = wave_count(cnt);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = wc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint64_t total = wsum[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) total += wsum[w];
+  if (FIN == kPlaneFinFrame)  // result unused: a no-return atomic, nothing waits for it in the block
+    __hip_atomic_fetch_add(reinterpret_cast<uint64_t*>(out) + (blockIdx.x % kFrameSlots) * kFrameSlotStride,
+                           pack_count((int64_t)total, 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    packed_count_finalize(ticket, groups, (int64_t)total, 0, out, nan_out, nb);
+}
+
+// kPlaneFinGeneral: the wave's count in lane 0's Acc, then every other finalize form
+__device__ __forceinline__ void plane_count_general(uint32_t cnt, const ScanLaunch& L) {
+  const uint64_t wc = wave_count(cnt);
+  Acc acc;
+  acc_init(acc);
+  acc.count = (threadIdx.x & 63) == 0 ? (int64_t)wc : 0;
+  block_reduce_store<false>(acc, L);
 }
 
 // Pack the 4-row nibbles of 16 consecutive lanes into one BitSet word.

@@ -9,6 +9,16 @@
 
 namespace mbx {
 
+// a lane's selected rows -> the block's arrival, in the launch's PlaneFin form
+// (plane_fin_of picks it on the host)
+template <int FIN>
+__device__ __forceinline__ void plane_finish(uint32_t cnt, const ScanLaunch& L) {
+  if constexpr (FIN == kPlaneFinGeneral)
+    plane_count_general(cnt, L);
+  else
+    plane_count_finish<FIN>(cnt, L.count_out, L.ticket, L.ticket_groups, L.nan_out);
+}
+
 // ------------------------------------------------------ sliced COUNT scan
 //
 // COUNT over byte-plane slices (mbx_table_slice): a wave's tile is 1024 rows,
@@ -176,7 +186,7 @@ __device__ __forceinline__ uint32_t sliced_tile(const KSliceTerm (&th)[kSliceMax
 // contiguous segment of sliced tiles dealt round-robin to its 4 waves.  The
 // planes are padded to a whole tile, so the table's partial tile loads like
 // any other and masks its rows.
-template <int K, bool DEL, int U>
+template <int K, bool DEL, int U, int FIN>
 __device__ __forceinline__ void scan_sliced_body(const ScanLaunch& L) {
   const KSlicePlan* __restrict__ S = L.sl;
   const int lane = threadIdx.x & 63;
@@ -236,26 +246,20 @@ __device__ __forceinline__ void scan_sliced_body(const ScanLaunch& L) {
     if (DEL && rem > 0) valid &= ~(uint32_t)del[tp * (kSliceTileRows / 16) + lane];
     cnt += sliced_tile<K, true>(th, nterms, cn, pl, first, pstride, x, tp, lane, slice_scatter16(valid));
   }
-  uint64_t wc = cnt;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) wc += __shfl_xor(wc, m);
-  Acc acc;
-  acc_init(acc);
-  acc.count = lane == 0 ? (int64_t)wc : 0;
-  block_reduce_store<false>(acc, L);
+  plane_finish<FIN>(cnt, L);
 }
 
-template <int K, bool DEL, int U>
+template <int K, bool DEL, int U, int FIN>
 __global__ __launch_bounds__(kBlock) void k_scan_sliced(ScanLaunch L) {
-  scan_sliced_body<K, DEL, U>(L);
+  scan_sliced_body<K, DEL, U, FIN>(L);
 }
 
 // The one- and two-column forms fit 8 waves per SIMD (k_scan_fast<2, COUNT>'s
 // occupancy) without scratch when the compiler is held to that register
 // budget; left alone it keeps ~100 loop-invariant scalars and stops at 7.
-template <int K, bool DEL, int U>
+template <int K, bool DEL, int U, int FIN>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_sliced8(ScanLaunch L) {
-  scan_sliced_body<K, DEL, U>(L);
+  scan_sliced_body<K, DEL, U, FIN>(L);
 }
 
 // key min / max of an int32 column (mm[0] preset to ~0u, mm[1] to 0)
@@ -438,23 +442,12 @@ __device__ __forceinline__ void bits_eval(const BitTerms& T, const SliceCnf& cn,
   }
 }
 
-// a lane's selected rows -> the wave's count -> the block's arrival
-__device__ __forceinline__ void bits_finish(uint32_t cnt, int lane, const ScanLaunch& L) {
-  uint64_t wc = cnt;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) wc += __shfl_xor(wc, m);
-  Acc acc;
-  acc_init(acc);
-  acc.count = lane == 0 ? (int64_t)wc : 0;
-  block_reduce_store<false>(acc, L);
-}
-
 // U tiles in flight per wave; a block owns a contiguous segment of bit tiles
 // dealt round-robin to its 4 waves (as scan_sliced_body).  The planes are
 // padded to a whole tile, so the table's partial tile loads like any other and
 // masks its rows; the deleted image is padded to 64 rows only, so the partial
 // tile reads it dword by dword and never past the table's last row.
-template <bool DEL, int U>
+template <bool DEL, int U, int FIN>
 __global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
   const KBitPlan* __restrict__ B = L.bp;
   const int lane = threadIdx.x & 63;
@@ -516,7 +509,7 @@ __global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
     bits_eval<1>(T, cn, dw, res);
     cnt += bit_popc(res[0] & live);
   }
-  bits_finish(cnt, lane, L);
+  plane_finish<FIN>(cnt, L);
 }
 
 // ------------------------------------------- shallow bit-plane COUNT scan
@@ -540,10 +533,23 @@ constexpr int bits1_batch(int np, bool del) {
   return np >= 4 ? 2 : 12 / (np + (del ? 1 : 0) > 0 ? np + (del ? 1 : 0) : 1);
 }
 
-struct Bits1Plan {
-  const uint32_t* pl[kSliceMaxTerms];  // slot k: plane 0 of the k-th term that reads one
+// k_scan_bits1's kernel arguments: what the kernel reads and nothing else of
+// ScanLaunch, 88 bytes, what the first plane load needs (rows, segment, plane
+// pointers, deleted image) in front -- one round of scalar loads and one wait
+// before that load.  The kernel finishes in the two hot forms only
+// (kPlaneFinPacked / kPlaneFinFrame); launch_scan_bits sends every other form
+// of a shallow plan to k_scan_bits.
+struct Bits1Launch {
+  int64_t nrows;
+  int32_t tiles_per_block;             // bit tiles; at most the table's, so tile numbers stay in 32 bits
   uint32_t table;                      // bit i: rows whose plane-k bit is bit k of i are selected
-  uint32_t pad_;
+  const uint32_t* pl[kSliceMaxTerms];  // slot k: plane 0 of the k-th term that reads one
+  const uint64_t* deleted;             // device or null
+  int64_t* out;                        // the count word (kPlaneFinPacked) / the count frame (kPlaneFinFrame)
+  uint32_t* ticket;                    // kPlaneFinPacked
+  int32_t* nan_out;
+  int32_t ticket_groups;
+  int32_t pad_;
 };
 
 // A term of depth <= 1 over plane 0 of its column (x: any value at depth 0)
@@ -559,9 +565,9 @@ __host__ __device__ __forceinline__ V bit_term1(uint32_t m, uint32_t lo, uint32_
 
 // Plane slots and truth table of a shallow plan: the predicate over probe
 // words, plane k's probe holding bit k of every index 0..15
-static Bits1Plan bits1_plan_of(const KBitPlan& B) {
+static Bits1Launch bits1_plan_of(const KBitPlan& B) {
   constexpr uint32_t kProbe[kSliceMaxTerms] = {0xAAAAu, 0xCCCCu, 0xF0F0u, 0xFF00u};
-  Bits1Plan P{};
+  Bits1Launch P{};
   uint32_t r[kSliceMaxTerms] = {0u, 0u, 0u, 0u};
   int slot = 0;
   for (int ti = 0; ti < B.nterms; ++ti) {
@@ -614,19 +620,32 @@ __device__ __forceinline__ v4u bit_tile_load(const uint32_t* p, int lane) {
 }
 
 // Segments, tile ownership, the partial tile and the deleted image as in
-// k_scan_bits; kB tiles per batch instead of U.
-template <int NP, bool DEL>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_bits1(ScanLaunch L,
-                                                                                                  Bits1Plan P) {
+// k_scan_bits; kB tiles per batch instead of U.  Tile numbers fit 32 bits
+// (rows < 2^40, and the host holds tiles_per_block to the table's tiles), so
+// the segment bounds and the loop's compares are 32-bit scalar arithmetic.
+// FIN: kPlaneFinPacked or kPlaneFinFrame.
+template <int NP, bool DEL, int FIN>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_bits1(Bits1Launch P) {
   constexpr int kB = bits1_batch(NP, DEL);
   constexpr int kNP = NP > 0 ? NP : 1, kC = 1 << (kNP - 1);
   constexpr int kTileDwords = kBitTileRows / 32;
+  // The epilogue's arguments, held in scalar registers from here on: left alone, hipcc loads them
+  // after the block's barrier, a scalar memory round trip between the last plane load and the
+  // block's atomic.  Here they ride in the one round of argument loads before the first plane load.
+  uint64_t out = reinterpret_cast<uint64_t>(P.out), ticket = reinterpret_cast<uint64_t>(P.ticket);
+  uint64_t nan_out = reinterpret_cast<uint64_t>(P.nan_out);
+  int32_t groups = P.ticket_groups;
+  uint32_t nblocks = gridDim.x;
+  if constexpr (FIN == kPlaneFinPacked)
+    asm volatile("" : "+s"(out), "+s"(ticket), "+s"(nan_out), "+s"(groups), "+s"(nblocks));
+  else
+    asm volatile("" : "+s"(out));
   const int lane = threadIdx.x & 63;
   const int wave = (int)uniform(threadIdx.x >> 6);
-  const int64_t nrows = L.nrows;
-  const int64_t ntiles = (nrows + kBitTileRows - 1) / kBitTileRows;
-  const int64_t t0 = (int64_t)blockIdx.x * L.tiles_per_block;
-  const int64_t t1 = min(t0 + L.tiles_per_block, ntiles);
+  const int tp = (int)(P.nrows / kBitTileRows);     // the full tiles = the partial tile's number
+  const int prows = (int)(P.nrows % kBitTileRows);  // the partial tile's rows
+  const int t0 = (int)blockIdx.x * P.tiles_per_block;
+  const int t1 = min(t0 + P.tiles_per_block, tp + (prows != 0 ? 1 : 0));
   const uint32_t* pl[kNP];
 #pragma unroll
   for (int k = 0; k < kNP; ++k) pl[k] = P.pl[k];
@@ -637,13 +656,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     lb[c] = f0 ? ~0u : 0u;
     la[c] = f0 != f1 ? ~0u : 0u;
   }
-  gu32* del = (gu32*)L.deleted;
-  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(L.deleted) & 15) == 0;  // uniform
+  gu32* del = (gu32*)P.deleted;
+  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(P.deleted) & 15) == 0;  // uniform
 
   uint32_t cnt = 0;
-  // full tiles in the main loop; tile numbers fit 32 bits (rows < 2^40), which keeps the loop's compares scalar
-  const int tf = (int)min(t1, nrows / kBitTileRows);
-  for (int base = (int)min(t0 + wave, (int64_t)tf); base < tf; base += kWaves * kB) {
+  const int tf = min(t1, tp);  // full tiles in the main loop
+  for (int base = min(t0 + wave, tf); base < tf; base += kWaves * kB) {
     v4u x[kB][kNP], dead[kB];
     // every load of the batch, unconditional; a tile past the full tiles is the last one again, and is not counted
     int64_t dw[kB];  // the tile's first dword in every plane (uniform)
@@ -657,11 +675,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     if (DEL) {
       if (del16) {
 #pragma unroll
-        for (int u = 0; u < kB; ++u) dead[u] = bit_tile_load(reinterpret_cast<const uint32_t*>(L.deleted) + dw[u], lane);
+        for (int u = 0; u < kB; ++u) dead[u] = bit_tile_load(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
       } else {
 #pragma unroll
         for (int u = 0; u < kB; ++u) {
-          gu32* d = (gu32*)bit_tile_lane(reinterpret_cast<const uint32_t*>(L.deleted) + dw[u], lane);
+          gu32* d = (gu32*)bit_tile_lane(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
 #pragma unroll
           for (int i = 0; i < 4; ++i) dead[u][i] = d[i];
         }
@@ -683,17 +701,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       cnt += base + u * kWaves < tf ? c : 0u;
     }
   }
-  const int64_t tp = nrows / kBitTileRows;  // the partial tile, owned like any other tile of [t0, t1)
-  if ((nrows % kBitTileRows) != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
+  // the partial tile, owned like any other tile of [t0, t1)
+  if (prows != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
     v4u xp[kNP];
     xp[0] = bit_splat(0u);
 #pragma unroll
-    for (int k = 0; k < NP; ++k) xp[k] = bit_tile_load(pl[k] + tp * kTileDwords, lane);
-    const int64_t dw = tp * kTileDwords + lane * 4;
+    for (int k = 0; k < NP; ++k) xp[k] = bit_tile_load(pl[k] + (int64_t)tp * kTileDwords, lane);
+    const int64_t dw = (int64_t)tp * kTileDwords + lane * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int64_t rem = nrows - (dw + i) * 32;  // the dword's rows below nrows
-      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << (int)rem) - 1u));
+      const int rem = prows - (lane * 4 + i) * 32;  // the dword's rows below nrows
+      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
       if (DEL && rem > 0) valid &= ~del[dw + i];
       uint32_t xi[kNP];
 #pragma unroll
@@ -701,7 +719,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       cnt += (uint32_t)__popc(bits1_rows<NP>(xi, la, lb) & valid);
     }
   }
-  bits_finish(cnt, lane, L);
+  plane_count_finish<FIN>(cnt, reinterpret_cast<int64_t*>(out), reinterpret_cast<uint32_t*>(ticket), groups,
+                          reinterpret_cast<int32_t*>(nan_out), nblocks);
 }
 
 // planes 0..w-1 of 64 rows per wave step: one ballot per plane, lane j stores
@@ -730,34 +749,68 @@ __global__ __launch_bounds__(kBlock) void k_bitslice_build(const int32_t* __rest
 #ifndef MBX_BITS_U
 #define MBX_BITS_U 2
 #endif
-template <int NP>
-static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
-  const Bits1Plan P = bits1_plan_of(B);
-  if (L.deleted)
-    hipLaunchKernelGGL((k_scan_bits1<NP, true>), grid, dim3(kBlock), 0, s, L, P);
-  else
-    hipLaunchKernelGGL((k_scan_bits1<NP, false>), grid, dim3(kBlock), 0, s, L, P);
+// The PlaneFin of a COUNT launch over planes.  The two hot forms -- the packed
+// in-launch finalize and the count frame -- have kernels that carry nothing
+// else; write-through (the fin_mode knob, or a grid packed_count_fits refuses),
+// kFinSegOnly, kFinSeparate / no ticket and a launch with segment counts take
+// the general form.
+static int plane_fin_of(const ScanLaunch& L) {
+  if (L.seg_counts) return kPlaneFinGeneral;
+  if (L.fin_mode == kFinFrame) return kPlaneFinFrame;
+  if (L.fin_mode == kFinPackedCount && L.ticket) return kPlaneFinPacked;
+  return kPlaneFinGeneral;
 }
 
-hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s) {
-  const dim3 grid((unsigned)blocks_for(L.nrows, kBitTileRows, L.tiles_per_block));
-  if (!shallow) {
-    if (L.deleted)
-      hipLaunchKernelGGL((k_scan_bits<true, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
-    else
-      hipLaunchKernelGGL((k_scan_bits<false, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
-    return hipGetLastError();
-  }
-  if (!bit_plan_shallow(*shallow)) return hipErrorInvalidValue;
-  switch (bit_plan_reads(*shallow)) {  // one plane per term that reads
-    case 0: bits1_launch<0>(L, *shallow, grid, s); break;
-    case 1: bits1_launch<1>(L, *shallow, grid, s); break;
-    case 2: bits1_launch<2>(L, *shallow, grid, s); break;
-    case 3: bits1_launch<3>(L, *shallow, grid, s); break;
-    case 4: bits1_launch<4>(L, *shallow, grid, s); break;
+template <int NP, int FIN>
+static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
+  Bits1Launch P = bits1_plan_of(B);
+  const int64_t ntiles = (L.nrows + kBitTileRows - 1) / kBitTileRows;
+  P.nrows = L.nrows;
+  P.tiles_per_block = (int32_t)std::min(L.tiles_per_block, std::max<int64_t>(ntiles, 1));  // the grid is the same
+  P.deleted = L.deleted;
+  P.out = L.count_out;
+  P.ticket = L.ticket;
+  P.nan_out = L.nan_out;
+  P.ticket_groups = L.ticket_groups;
+  if (L.deleted)
+    hipLaunchKernelGGL((k_scan_bits1<NP, true, FIN>), grid, dim3(kBlock), 0, s, P);
+  else
+    hipLaunchKernelGGL((k_scan_bits1<NP, false, FIN>), grid, dim3(kBlock), 0, s, P);
+}
+
+template <int FIN>
+static hipError_t bits1_launch_np(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
+  switch (bit_plan_reads(B)) {  // one plane per term that reads
+    case 0: bits1_launch<0, FIN>(L, B, grid, s); break;
+    case 1: bits1_launch<1, FIN>(L, B, grid, s); break;
+    case 2: bits1_launch<2, FIN>(L, B, grid, s); break;
+    case 3: bits1_launch<3, FIN>(L, B, grid, s); break;
+    case 4: bits1_launch<4, FIN>(L, B, grid, s); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+template <int FIN>
+static hipError_t bits_launch(const ScanLaunch& L, dim3 grid, hipStream_t s) {
+  if (L.deleted)
+    hipLaunchKernelGGL((k_scan_bits<true, MBX_BITS_U, FIN>), grid, dim3(kBlock), 0, s, L);
+  else
+    hipLaunchKernelGGL((k_scan_bits<false, MBX_BITS_U, FIN>), grid, dim3(kBlock), 0, s, L);
+  return hipGetLastError();
+}
+
+// shallow: the plan's host copy when its launch is k_scan_bits1's.  That kernel
+// exists in the two hot forms only; a shallow plan's launch in the general form
+// is k_scan_bits', which takes every bit plan (L.bp).
+hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s) {
+  const dim3 grid((unsigned)blocks_for(L.nrows, kBitTileRows, L.tiles_per_block));
+  const int fin = plane_fin_of(L);
+  if (shallow && !bit_plan_shallow(*shallow)) return hipErrorInvalidValue;
+  if (fin == kPlaneFinGeneral) return bits_launch<kPlaneFinGeneral>(L, grid, s);
+  if (fin == kPlaneFinFrame)
+    return shallow ? bits1_launch_np<kPlaneFinFrame>(L, *shallow, grid, s) : bits_launch<kPlaneFinFrame>(L, grid, s);
+  return shallow ? bits1_launch_np<kPlaneFinPacked>(L, *shallow, grid, s) : bits_launch<kPlaneFinPacked>(L, grid, s);
 }
 
 hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,
@@ -770,31 +823,40 @@ hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t bas
 
 // tiles in flight per wave: the same KiB as k_scan_fast's U over 256-row tiles
 // (prod_launch, mbx_scan_mode.hpp: 4 / MBX_SCAN_U2 / kDefaultU for 1 / 2 / more columns)
-template <int K>
+template <int K, int FIN>
 void sliced_launch(const ScanLaunch& L, dim3 grid, hipStream_t s) {
   constexpr int kU = K == 1 ? 4 : (K == 2 ? MBX_SCAN_U2 : kDefaultU);
   if (L.deleted) {
     if constexpr (K == 1)
-      hipLaunchKernelGGL((k_scan_sliced8<K, true, kU>), grid, dim3(kBlock), 0, s, L);
+      hipLaunchKernelGGL((k_scan_sliced8<K, true, kU, FIN>), grid, dim3(kBlock), 0, s, L);
     else
-      hipLaunchKernelGGL((k_scan_sliced<K, true, kU>), grid, dim3(kBlock), 0, s, L);
+      hipLaunchKernelGGL((k_scan_sliced<K, true, kU, FIN>), grid, dim3(kBlock), 0, s, L);
   } else if constexpr (K <= 2) {
-    hipLaunchKernelGGL((k_scan_sliced8<K, false, kU>), grid, dim3(kBlock), 0, s, L);
+    hipLaunchKernelGGL((k_scan_sliced8<K, false, kU, FIN>), grid, dim3(kBlock), 0, s, L);
   } else {
-    hipLaunchKernelGGL((k_scan_sliced<K, false, kU>), grid, dim3(kBlock), 0, s, L);
+    hipLaunchKernelGGL((k_scan_sliced<K, false, kU, FIN>), grid, dim3(kBlock), 0, s, L);
   }
+}
+
+template <int FIN>
+static hipError_t sliced_launch_k(const ScanLaunch& L, int32_t ncols, dim3 grid, hipStream_t s) {
+  switch (ncols) {
+    case 1: sliced_launch<1, FIN>(L, grid, s); break;
+    case 2: sliced_launch<2, FIN>(L, grid, s); break;
+    case 3: sliced_launch<3, FIN>(L, grid, s); break;
+    case 4: sliced_launch<4, FIN>(L, grid, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_scan_sliced(const ScanLaunch& L, int32_t ncols, hipStream_t s) {
   const dim3 grid((unsigned)blocks_for(L.nrows, kSliceTileRows, L.tiles_per_block));
-  switch (ncols) {
-    case 1: sliced_launch<1>(L, grid, s); break;
-    case 2: sliced_launch<2>(L, grid, s); break;
-    case 3: sliced_launch<3>(L, grid, s); break;
-    case 4: sliced_launch<4>(L, grid, s); break;
-    default: return hipErrorInvalidValue;
+  switch (plane_fin_of(L)) {
+    case kPlaneFinPacked: return sliced_launch_k<kPlaneFinPacked>(L, ncols, grid, s);
+    case kPlaneFinFrame: return sliced_launch_k<kPlaneFinFrame>(L, ncols, grid, s);
+    default: return sliced_launch_k<kPlaneFinGeneral>(L, ncols, grid, s);
   }
-  return hipGetLastError();
 }
 
 hipError_t launch_slice_minmax(const int32_t* col, int64_t nrows, uint32_t* mm, hipStream_t s) {

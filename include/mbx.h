@@ -191,7 +191,8 @@ int mbx_table_group(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t nco
  * [0, 2^20) keep 3 planes, [256, 511] keeps 1).  COUNT scans of plans bound
  * to the slices (mbx_plan_compile) read planes top-down and only as deep as
  * some row still needs: `c < 2^19` over [0, 2^20) reads 1 byte per row
- * instead of 4.  Results are identical; BitSet, select and aggregate scans
+ * instead of 4.  Results are identical; aggregate scans, and the BitSet and
+ * select scans of every plan not bound to bit planes (mbx_plan_bitmap_form),
  * keep reading the columns.  Costs one read of the column, and stored-planes
  * bytes x nrows of HBM, once per column.  A slice is a snapshot taken at
  * this call: for a table over caller memory (mbx_table_wrap) whose columns
@@ -248,6 +249,15 @@ int mbx_bitslice_bound(uint32_t kmin, uint32_t kmax, uint32_t key, int32_t upper
  * [0, 2^20), which reads 1 bit per row), the bit planes the plan reads are
  * built here if they do not exist yet -- adding them to a slice unbinds no
  * plan -- and its COUNT scans are bound to them instead of the byte planes.
+ * So are its BitSet scans (mbx_scan_bitmap, _async, mbx_scan_select, the
+ * two-launch form of mbx_scan_select_async, and the cursors and drop-ins on
+ * top of them; mbx_plan_bitmap_form = 2): the BitSet's words are the planes'
+ * row order, so the scan reads the planes the COUNT reads and writes the same
+ * words and segment counts as the column scan, with no allocation at launch
+ * (capturable in a HIP graph).  The snapshot rule above covers them: over
+ * rewritten mbx_table_wrap memory the BitSet keeps the values of this call
+ * until mbx_table_slice drops or rebuilds the slices, after which the plan's
+ * BitSet scans read the live columns again.
  * Other plans, plans compiled under a capture while planes are missing, and
  * plans whose bit planes cannot be allocated take the byte planes;
  * auto_bitslice = 0 binds every plan as if there were no bit planes. */
@@ -257,8 +267,22 @@ int mbx_plan_free(mbx_plan *p);
  * kernel (bound at compile, slices not dropped or rebuilt since), else 0 */
 int mbx_plan_sliced(mbx_ctx *ctx, const mbx_plan *p, int32_t *sliced);
 /* *form = what COUNT launches of this plan currently read: 0 the columns,
- * 1 byte planes, 2 bit planes (mbx_plan_sliced reports 1 for both 1 and 2) */
+ * 1 byte planes, 2 bit planes (mbx_plan_sliced reports 1 for both 1 and 2).
+ * COUNT only: mbx_plan_bitmap_form answers for the BitSet scans. */
 int mbx_plan_slice_form(mbx_ctx *ctx, const mbx_plan *p, int32_t *form);
+/* *form = what BitSet scans of this plan (mbx_scan_bitmap, _async, and the
+ * two-launch select scans: mbx_scan_select, mbx_scan_select_async under
+ * scan_select_fused = 0 or for a plan its one-launch form does not take)
+ * currently read: 0 the columns, 2 bit planes (k_scan_bits_words) -- a plan
+ * whose mbx_plan_slice_form is 2, over a table of at least one row and, when
+ * some bound is decided deeper than its column's top kept bit
+ * (mbx_plan_bit_shallow's rule, whatever the bits_shallow knob), of at least
+ * 2^25 rows with at most 8 planes read per column: below that the column scan
+ * measured faster.  The tuning knob bitmap_plane_floor
+ * (>= 0) replaces both conditions by a row floor; it is read at each launch,
+ * and this function reports what a launch now would take.  A plan on byte
+ * planes (form 1) reports 0: its BitSet scans read the columns. */
+int mbx_plan_bitmap_form(mbx_ctx *ctx, const mbx_plan *p, int32_t *form);
 /* *shallow = 1 when COUNT launches of this plan currently take the shallow
  * bit-plane kernel (k_scan_bits1): form 2, every bound of every term decided
  * on its column's top kept bit (mbx_bitslice_bound: *depth <= 1), and the
@@ -514,8 +538,10 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * "join_plain", "join_chunk_words" (pair-matrix words per chunk of mbx_join, 1 .. 2^24; anything else: 2^24),
  * "distinct_lds_probes", "gather_fused", "gather_pair" (0: two 4-byte loads per grouped pair row),
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
- * "comm_same_stream", "scan_words_wt", "auto_slice", "auto_bitslice" (mbx_plan_compile above),
- * "bits_shallow" (0: every bit-plane plan takes k_scan_bits; read at launch), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
+ * "comm_same_stream", "scan_words_wt" (the column scans' BitSet words write-through; the bit-plane BitSet scan
+ * does not honour it and always stores plain), "auto_slice", "auto_bitslice" (mbx_plan_compile above),
+ * "bits_shallow" (0: every bit-plane plan takes k_scan_bits; read at launch), "bitmap_plane_floor" (rows from which
+ * BitSet launches of a bit-bound plan take the planes, mbx_plan_bitmap_form above; -1: the built-in rule), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,
  * 2 write-through, 3 nontemporal); "reset" restores the defaults. */
 int mbx_set_tuning(mbx_ctx *ctx, const char *knob, int64_t value);

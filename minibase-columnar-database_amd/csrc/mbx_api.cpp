@@ -110,6 +110,7 @@ static void tuning_defaults(MbxTuning& t) {
   t.auto_slice = env_knob("MBX_AUTO_SLICE", 1) != 0;
   t.auto_bitslice = env_knob("MBX_AUTO_BITSLICE", 1) != 0;
   t.bits_shallow = env_knob("MBX_BITS_SHALLOW", 1) != 0;
+  t.bitmap_plane_floor = env_knob("MBX_BITMAP_PLANE_FLOOR", -1);
   t.cnf_blocks = (int32_t)env_knob("MBX_CNF_BLOCKS", 0);
   t.cnf_flag_stride = env_knob("MBX_CNF_FLAG_STRIDE", 1) == kFlagStride ? kFlagStride : 1;
   t.cnf_lookback = (int32_t)env_knob("MBX_CNF_LOOKBACK", 0);
@@ -344,6 +345,7 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
   else if (!strcmp(knob, "auto_slice")) t.auto_slice = v != 0;
   else if (!strcmp(knob, "auto_bitslice")) t.auto_bitslice = v != 0;
   else if (!strcmp(knob, "bits_shallow")) t.bits_shallow = v != 0;
+  else if (!strcmp(knob, "bitmap_plane_floor")) t.bitmap_plane_floor = v < 0 ? -1 : v;
   else return fail(MBX_E_INVALID, "mbx_set_tuning: unknown knob `%s`", knob);
   return MBX_OK;
 }
@@ -1071,6 +1073,7 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                         Partial* parts, const ScanGeometry& g, int64_t* count_out, AggOut* agg_out,
                         int32_t* nan_out, const ScanOpts& o = ScanOpts()) {
   // g.form kFormBytes / kFormBits: g.tpb counts sliced / bit tiles and the launch is the plan's plane scan
+  // (kModeBitmap over bit planes: 256-row tiles, the bitmap's segments)
   const int64_t tpb = g.tpb, nb = g.nb;
   ScanLaunch L;
   L.plan = v.dev;
@@ -1290,7 +1293,9 @@ static int scan_bitmap_into(mbx_ctx* c, mbx_plan* p, mbx_bitmap* b, int32_t* dev
   PlanVariant* v = nullptr;
   int rc = plan_variant(p, -1, &v);
   if (rc) return rc;
-  const ScanGeometry g = column_geometry(p, b->wpb / kWordsPerTile);
+  // a bit-bound plan's BitSet comes from its planes (k_scan_bits_words), one block per segment of
+  // the bitmap as the column scan; every other plan reads the columns
+  const ScanGeometry g = bitmap_geometry(p, b->wpb / kWordsPerTile);
   if (g.nb != b->nseg) return fail(MBX_E_INVALID, "scan_bitmap: segment mismatch");
   if ((rc = ensure_partials(c, b->nseg))) return rc;
   ScanOpts o;

@@ -154,12 +154,14 @@ struct ScanLaunch {
                               //    (tiles_per_block x 32 B) and stored in one burst at the block's end
   int64_t* seg_counts;        // BitSet scans: the output bitmap's per-segment counts (one per block)
   int32_t words_wt;           // BitSet words stored write-through (sc1) instead of plain
+                              // (the column scans; k_scan_bits_words always stores plain)
   int32_t int_range;          // branch-free range-test term body: 1 every term an int literal
                               // compare, 2 literal compares of any type (int / float / char(16))
   const struct KSlicePlan* sl = nullptr;  // sliced COUNT scan (k_scan_sliced): device; tiles_per_block
                                           // then counts sliced tiles (kSliceTileRows rows)
   const struct KBitPlan* bp = nullptr;    // bit-plane COUNT scan (k_scan_bits): device; tiles_per_block
-                                          // then counts bit tiles (kBitTileRows rows)
+                                          // then counts bit tiles (kBitTileRows rows).  The bit-plane
+                                          // BitSet scan (k_scan_bits_words) keeps 256-row tiles
 };
 
 // ---- byte-plane slices of int32 columns (mbx_table_slice)
@@ -503,6 +505,10 @@ hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, 
 // with bit_plan_shallow (its launch is k_scan_bits1, which takes what it needs of the plan in its
 // kernel arguments), or null (k_scan_bits, which reads L.bp)
 hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s);
+// bit-plane BitSet scan (k_scan_bits_words): L.bp set; the grid is the output bitmap's, so
+// L.tiles_per_block keeps its 256-row meaning (a segment of tiles_per_block x 4 words); writes
+// every word of L.out_words and L.seg_counts[block].  L.words_wt is not honoured: plain stores
+hipError_t launch_scan_bits_words(const ScanLaunch& L, hipStream_t s);
 // planes 0..w-1 (bits h..h-w+1 of key - base) of the column into out, plane j at
 // out + j * pstride dwords; pstride = rows padded to a whole bit tile / 32, the padding written as 0
 hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,

@@ -69,7 +69,8 @@ struct MbxTuning {
   int32_t scan_select_fused = 1;  // MBX_SCAN_SELECT_FUSED: 1 = BitSet + positions in one launch (k_scan_select)
   int32_t scan_select_waves = 16; // MBX_SCAN_SELECT_WAVES: waves per k_scan_select block (4 or 16)
   int32_t select_flag_stride = 16; // MBX_SELECT_FLAG_STRIDE: 16 = k_scan_select's polled flags one per line, or 1
-  int32_t scan_words_wt = 1;      // MBX_SCAN_WORDS_WT: BitSet scan words stored write-through
+  int32_t scan_words_wt = 1;      // MBX_SCAN_WORDS_WT: BitSet scan words stored write-through (the column scans;
+                                  // the bit-plane BitSet scan, k_scan_bits_words, does not honour it: plain stores)
   int32_t comm_same_stream = 1;   // MBX_COMM_SAME_STREAM: collectives on the context stream (0: the exchange stream)
   int32_t auto_slice = 1;         // MBX_AUTO_SLICE: mbx_plan_compile builds byte-plane slices of the int32 columns of a
                                   // slice-eligible plan and binds its COUNT scans to them (0: plans read the columns)
@@ -77,7 +78,10 @@ struct MbxTuning {
                                   // bit planes binds to those (k_scan_bits); 0: every sliced plan takes the byte planes
   int32_t bits_shallow = 1;       // MBX_BITS_SHALLOW: a bit-plane plan whose every term has depth <= 1 takes
                                   // k_scan_bits1 (read at launch); 0: every bit-plane plan takes k_scan_bits
-  int32_t select_dbg = 0;         // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
+  int64_t bitmap_plane_floor = -1; // MBX_BITMAP_PLANE_FLOOR: rows from which BitSet launches of a bit-bound plan take the
+                                  // planes (k_scan_bits_words; read at launch).  -1: shallow plans always, deep plans from
+                                  // 2^25 rows and <= 8 planes per column (mbx_planes.cpp); 0: every bit-bound plan
+  int32_t select_dbg = 0;        // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
                                   // instead of the chained look-back, 512 write-through flip; -DMBX_DIAG
                                   // builds only: k_select_ids bit 0 no prefix / bit 1 no emission, the
                                   // one-launch selections' 16 back-off / 32 no wait / 64 plain-load polls
@@ -150,9 +154,10 @@ struct mbx_table {
 // how COUNT launches of a plan read the table (mbx_plan_slice_form)
 enum SliceForm : int32_t { kFormColumns = 0, kFormBytes = 1, kFormBits = 2 };
 
-// A plan's COUNT scans bound to planes of its table's columns (mbx_planes.cpp).
-// It holds while gen is the table's slice_gen; a plan bound to an older
-// generation, or never bound (kFormColumns), scans the columns.
+// A plan's COUNT scans -- and, for kFormBits, its BitSet scans
+// (mbx_plan_bitmap_form) -- bound to planes of its table's columns
+// (mbx_planes.cpp).  It holds while gen is the table's slice_gen; a plan bound
+// to an older generation, or never bound (kFormColumns), scans the columns.
 struct PlaneBinding {
   int32_t form = kFormColumns;
   void* dev = nullptr;  // device KSlicePlan (kFormBytes: k_scan_sliced) / KBitPlan (kFormBits: k_scan_bits)
@@ -163,6 +168,7 @@ struct PlaneBinding {
 
 // segment size and grid of one scan launch: tpb tiles per block -- 256-row
 // tiles for kFormColumns, sliced tiles for kFormBytes, bit tiles for kFormBits
+// (a BitSet launch keeps 256-row tiles in every form: bitmap_geometry)
 struct ScanGeometry {
   int32_t form;
   int64_t tpb, nb;
@@ -259,9 +265,12 @@ bool plan_has_real(const mbx_plan* p);
 // mbx_planes.cpp.  bind_planes: mbx_plan_compile's last step -- binds the COUNT
 // scans of a slice-eligible plan to its columns' planes (building missing ones);
 // count_geometry: the plan's COUNT launch, given the column scan's tpb;
-// launch_plane_scan: that launch for g.form != kFormColumns (sets L.sl / L.bp)
+// bitmap_geometry: the plan's BitSet launch into a bitmap of tpb-tile segments
+// (kFormBits: k_scan_bits_words over the same grid as the column scan's);
+// launch_plane_scan: either launch for g.form != kFormColumns (sets L.sl / L.bp)
 void bind_planes(mbx_ctx* c, mbx_plan* p);
 ScanGeometry count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tpb);
+ScanGeometry bitmap_geometry(const mbx_plan* p, int64_t tpb);
 hipError_t launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s);
 // mbx_comm.cpp: mbx_sync / mbx_free of a context with a communicator
 int comm_sync(mbx_ctx* c);

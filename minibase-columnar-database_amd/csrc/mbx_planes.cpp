@@ -1,9 +1,10 @@
 // mbx_planes.cpp -- host side of the plane scans (mbx_planes.hip): byte-plane
 // slices and bit planes of int32 columns (mbx_table_slice), the binding of a
-// plan's COUNT scans to them at mbx_plan_compile, and the geometry and launch
-// of a bound plan's COUNT.  The planes are another layout of what
-// ColumnarFileScan.get_next reads (R/iterator/ColumnarFileScan.java:156-172);
-// which layout a COUNT reads never changes its result.
+// plan's COUNT scans (and a bit-bound plan's BitSet scans) to them at
+// mbx_plan_compile, and the geometry and launch of a bound plan's scans.  The
+// planes are another layout of what ColumnarFileScan.get_next reads
+// (R/iterator/ColumnarFileScan.java:156-172); which layout a scan reads never
+// changes its result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -360,6 +361,36 @@ ScanGeometry mbx::count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tp
   return ScanGeometry{form, tpb, blocks_for(nrows, tile_rows, tpb)};
 }
 
+// What BitSet launches of the plan read now (mbx_plan_bitmap_form): the bit
+// planes of a bit-bound plan under the COUNT's generation rule, the columns for
+// every other plan (byte-plane plans included) and for an empty table.
+//
+// A deep plan (some term of depth > 1) walks a term's planes one after the
+// other, a chain of dependent loads per wave that a small table cannot hide:
+// `c < 77` over [0, 200) (8 planes), builder box, 10 M rows: 15.2 us from the
+// planes against 8.9 from the column; 100 M: 31.8 against 65.2
+// (profiles/bitmap_planes).  The two lines cross near 24 M rows, so such a plan
+// keeps the columns below kBitmapDeepFloorRows, and whenever its planes are
+// more than a quarter of its columns' bytes (8 planes per column: the measured
+// case) -- four depth-8 terms on one column read as many bytes as the column.
+// Shallow plans (C3: 9.6 against 13.8 us at 10 M rows) have no floor.  The
+// bitmap_plane_floor knob (>= 0) replaces both conditions by a row floor.
+constexpr int64_t kBitmapDeepFloorRows = int64_t(1) << 25;
+static int32_t bitmap_form_now(const mbx_plan* p) {
+  if (plan_form_now(p) != kFormBits || p->t->nrows <= 0) return kFormColumns;
+  const int64_t knob = p->ctx->tune.bitmap_plane_floor;
+  if (knob >= 0) return p->t->nrows >= knob ? kFormBits : kFormColumns;
+  if (bit_plan_shallow(p->planes.bits)) return kFormBits;
+  return p->t->nrows >= kBitmapDeepFloorRows && p->planes.n <= 8 * (int32_t)p->slot_col.size() ? kFormBits
+                                                                                             : kFormColumns;
+}
+
+// The BitSet scan's grid is its output bitmap's in either form: segments of tpb
+// 256-row tiles (4 words each), one block per segment.
+ScanGeometry mbx::bitmap_geometry(const mbx_plan* p, int64_t tpb) {
+  return ScanGeometry{bitmap_form_now(p), tpb, grid_blocks(p->t->nrows, tpb)};
+}
+
 // a bit-plane plan's launch is the shallow kernel's (mbx_plan_bit_shallow)
 static bool takes_shallow(const mbx_plan* p) {
   return p->ctx->tune.bits_shallow != 0 && bit_plan_shallow(p->planes.bits);
@@ -368,8 +399,10 @@ static bool takes_shallow(const mbx_plan* p) {
 hipError_t mbx::launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s) {
   if (form == kFormBits) {
     L.bp = (const KBitPlan*)p->planes.dev;
+    if (L.mode == kModeBitmap) return launch_scan_bits_words(L, s);
     return launch_scan_bits(L, takes_shallow(p) ? &p->planes.bits : nullptr, s);
   }
+  if (L.mode != kModeCount) return hipErrorInvalidValue;  // the byte planes answer COUNT only
   L.sl = (const KSlicePlan*)p->planes.dev;
   return launch_scan_sliced(L, p->planes.n, s);
 }
@@ -387,6 +420,14 @@ extern "C" int mbx_plan_slice_form(mbx_ctx* c, const mbx_plan* p, int32_t* form)
   NOTNULL(p);
   NOTNULL(form);
   *form = plan_form_now(p);
+  return MBX_OK;
+}
+
+extern "C" int mbx_plan_bitmap_form(mbx_ctx* c, const mbx_plan* p, int32_t* form) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(form);
+  *form = bitmap_form_now(p);
   return MBX_OK;
 }
 

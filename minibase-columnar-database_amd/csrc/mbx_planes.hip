@@ -1,8 +1,9 @@
 // mbx_planes.hip -- COUNT scans over byte planes (k_scan_sliced) and bit
-// planes (k_scan_bits, k_scan_bits1, BitWeaving/V) of int32 columns, and the kernels that
+// planes (k_scan_bits, k_scan_bits1, BitWeaving/V) of int32 columns, the BitSet
+// scan over bit planes (k_scan_bits_words), and the kernels that
 // build the planes.  The scans answer what ColumnarFileScan.get_next
-// (R/iterator/ColumnarFileScan.java:156-172) counts, reading only the bytes
-// or bits of each row that decide the predicate.
+// (R/iterator/ColumnarFileScan.java:156-172) counts, or which rows it returns,
+// reading only the bytes or bits of each row that decide the predicate.
 #include <type_traits>
 
 #include "mbx_device.hpp"
@@ -374,7 +375,8 @@ __host__ __device__ __forceinline__ SliceCnf bit_cnf_of(const KBitPlan& B) {
   return cn;
 }
 
-// The selected rows of U tiles; dw[u]: the lane's first dword of tile u in every plane
+// The selected rows of U tiles (k_scan_bits) or of U 128-row chunks anywhere in the planes
+// (k_scan_bits_words); dw[u]: the lane's first dword of tile / chunk u in every plane
 template <int U>
 __device__ __forceinline__ void bits_eval(const BitTerms& T, const SliceCnf& cn, const int64_t (&dw)[U],
                                           v4u (&res)[U]) {
@@ -510,6 +512,113 @@ __global__ __launch_bounds__(kBlock) void k_scan_bits(ScanLaunch L) {
     cnt += bit_popc(res[0] & live);
   }
   plane_finish<FIN>(cnt, L);
+}
+
+// --------------------------------------------------- bit-plane BitSet scan
+//
+// The BitSet of a bit-plane plan (mbx_scan_bitmap and the scans behind it): the
+// rows bits_eval selects are already a lane's 128 bits of the BitSet in word
+// order, so the kernel stores them where k_scan_bits counts them.  The grid is
+// the output bitmap's: block s owns words [s * wpb, (s + 1) * wpb) of it, wpb =
+// tiles_per_block (256-row tiles here) x 4 words, which need not be a whole bit
+// tile.  The unit is therefore a lane's 16-byte chunk -- 2 words, 128 rows, 4
+// dwords of every plane -- and a wave step is 64 consecutive chunks (1 KiB per
+// plane); a block's steps are dealt round-robin to its 4 waves, U in flight.  A
+// segment starts on a 32-byte boundary of the words and of every plane, and the
+// planes are padded to a whole bit tile, so every chunk load is aligned and in
+// bounds.  Every word of the segment is stored, zero words included, with the
+// rows at or past nrows cleared (a negated or always-true term selects the
+// planes' padding); a lane counts what it stored and the block's count goes to
+// seg_counts[block] in the general PlaneFin form.
+typedef __attribute__((address_space(1))) v4u gv4u_out;
+typedef __attribute__((address_space(1))) uint64_t gu64_out;
+
+// the rows below nrows of the four dwords that start at dword dw
+__device__ __forceinline__ v4u bit_rows_below(int64_t nrows, int64_t dw) {
+  v4u live = bit_splat(~0u);
+  const int64_t rem = nrows - dw * 32;
+  if (rem < 128) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = (int)rem - 32 * i;
+      live[i] = r >= 32 ? ~0u : (r <= 0 ? 0u : ((1u << r) - 1u));
+    }
+  }
+  return live;
+}
+
+template <bool DEL, int U>
+__global__ __launch_bounds__(kBlock) void k_scan_bits_words(ScanLaunch L) {
+  const KBitPlan* __restrict__ B = L.bp;
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)uniform(threadIdx.x >> 6);
+  const int64_t nrows = L.nrows;
+  const int64_t nwords = (nrows + 63) >> 6;
+  const int64_t w0 = (int64_t)blockIdx.x * L.tiles_per_block * kWordsPerTile;
+  const int64_t w1 = min(w0 + L.tiles_per_block * kWordsPerTile, nwords);
+  BitTerms T;  // as k_scan_bits (a helper shared with it changed that kernel's code)
+  T.nterms = B->nterms;
+  T.pstride = B->pstride;
+#pragma unroll
+  for (int ti = 0; ti < kSliceMaxTerms; ++ti) {
+    T.pl[ti] = B->terms[ti].planes;
+    T.lo[ti] = B->terms[ti].lo;
+    T.hi[ti] = B->terms[ti].hi;
+    T.meta[ti] = B->terms[ti].meta;
+  }
+  const SliceCnf cn = bit_cnf_of(*B);
+  gu32* del = (gu32*)L.deleted;
+  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(L.deleted) & 15) == 0;  // uniform
+
+  uint32_t cnt = 0;
+  // whole chunks [c0, cf); an odd last word of the table (w1 == nwords) is the half chunk cf
+  const int64_t c0 = w0 >> 1, cf = w1 >> 1;
+  const int64_t nsteps = (cf - c0 + 63) >> 6;
+  for (int64_t base = wave; base < nsteps; base += (int64_t)kWaves * U) {
+    int64_t dw[U];
+    v4u dead[U], res[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // clamped: every path issues the same loads
+      int64_t ch = c0 + (base + (int64_t)u * kWaves) * 64 + lane;
+      ch = ch < cf ? ch : cf - 1;
+      dw[u] = ch * 4;
+      if (DEL) {  // a whole chunk lies within the image's nwords words
+        if (del16) {
+          dead[u] = __builtin_nontemporal_load((gv4u*)(del + dw[u]));
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dead[u][i] = del[dw[u] + i];
+        }
+      }
+    }
+    bits_eval<U>(T, cn, dw, res);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (c0 + (base + (int64_t)u * kWaves) * 64 + lane < cf) {
+        v4u m = res[u] & bit_rows_below(nrows, dw[u]);
+        if (DEL) m &= ~dead[u];
+        *(gv4u_out*)(reinterpret_cast<uint32_t*>(L.out_words) + dw[u]) = m;
+        cnt += bit_popc(m);
+      }
+  }
+  // the half chunk: the table's odd last word, stored alone -- its chunk's second word lies outside
+  // the bitmap and the deleted image.  Every lane of the next wave in turn loads the chunk, lane 0 keeps it.
+  if ((w1 & 1) != 0 && w1 > w0 && wave == (int)(nsteps % kWaves)) {
+    int64_t dw[1] = {cf * 4};
+    v4u res[1];
+    bits_eval<1>(T, cn, dw, res);
+    const v4u live = bit_rows_below(nrows, dw[0]);
+    uint32_t lo = res[0][0] & live[0], hi = res[0][1] & live[1];
+    if (DEL) {
+      lo &= ~del[dw[0]];
+      hi &= ~del[dw[0] + 1];
+    }
+    if (lane == 0) {
+      *(gu64_out*)(L.out_words + w1 - 1) = (uint64_t)lo | ((uint64_t)hi << 32);
+      cnt += (uint32_t)(__popc(lo) + __popc(hi));
+    }
+  }
+  plane_count_general(cnt, L);
 }
 
 // ------------------------------------------- shallow bit-plane COUNT scan
@@ -811,6 +920,16 @@ hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStr
   if (fin == kPlaneFinFrame)
     return shallow ? bits1_launch_np<kPlaneFinFrame>(L, *shallow, grid, s) : bits_launch<kPlaneFinFrame>(L, grid, s);
   return shallow ? bits1_launch_np<kPlaneFinPacked>(L, *shallow, grid, s) : bits_launch<kPlaneFinPacked>(L, grid, s);
+}
+
+hipError_t launch_scan_bits_words(const ScanLaunch& L, hipStream_t s) {
+  if (!L.bp || !L.out_words || !L.seg_counts || L.nrows <= 0 || L.tiles_per_block <= 0) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)grid_blocks(L.nrows, L.tiles_per_block));
+  if (L.deleted)
+    hipLaunchKernelGGL((k_scan_bits_words<true, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+  else
+    hipLaunchKernelGGL((k_scan_bits_words<false, MBX_BITS_U>), grid, dim3(kBlock), 0, s, L);
+  return hipGetLastError();
 }
 
 hipError_t launch_bitslice_build(const int32_t* col, int64_t nrows, uint32_t base, int32_t h, int32_t w,

@@ -81,7 +81,7 @@ def java_mutf8(s):
 EXPORTS = [
     "mbx_abi_version", "mbx_last_error", "mbx_device_count", "mbx_init", "mbx_free", "mbx_sync", "mbx_stream",
     "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_table_slice", "mbx_table_slice_info", "mbx_table_bitslice_info", "mbx_bitslice_range", "mbx_bitslice_bound",
-    "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced", "mbx_plan_slice_form", "mbx_plan_bit_shallow",
+    "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced", "mbx_plan_slice_form", "mbx_plan_bitmap_form", "mbx_plan_bit_shallow",
     "mbx_scan_count", "mbx_scan_count_async", "mbx_scan_count_frame_async", "mbx_count_frame_decode",
     "mbx_count_frame_fits",
     "mbx_scan_blocks", "mbx_scan_bitmap", "mbx_scan_bitmap_async", "mbx_scan_select",
@@ -155,6 +155,7 @@ def lib():
         "mbx_table_slice_info": ([V, I32, P(I32)], ctypes.c_int),
         "mbx_plan_sliced": ([V, V, P(I32)], ctypes.c_int),
         "mbx_plan_slice_form": ([V, V, P(I32)], ctypes.c_int),
+        "mbx_plan_bitmap_form": ([V, V, P(I32)], ctypes.c_int),
         "mbx_plan_bit_shallow": ([V, V, P(I32)], ctypes.c_int),
         "mbx_table_bitslice_info": ([V, I32, P(I32)], ctypes.c_int),
         "mbx_bitslice_range": ([ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32), P(I32), P(I32)], ctypes.c_int),
@@ -444,6 +445,14 @@ class Context:
         columns, 1 byte planes, 2 bit planes."""
         n = ctypes.c_int32()
         _chk(lib().mbx_plan_slice_form(self.h, plan.h, ctypes.byref(n)))
+        return n.value
+
+    def plan_bitmap_form(self, plan):
+        """mbx_plan_bitmap_form: what the plan's BitSet and two-launch select
+        scans read now -- 0 the columns, 2 bit planes (a bit-bound plan; a deep
+        one only from 2^25 rows, or from the bitmap_plane_floor knob's rows)."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_plan_bitmap_form(self.h, plan.h, ctypes.byref(n)))
         return n.value
 
     def plan_bit_shallow(self, plan):

@@ -288,6 +288,29 @@ int mbx_plan_bitmap_form(mbx_ctx *ctx, const mbx_plan *p, int32_t *form);
  * on its column's top kept bit (mbx_bitslice_bound: *depth <= 1), and the
  * tuning knob bits_shallow (default 1) not 0; else 0.  The form is 2 either way. */
 int mbx_plan_bit_shallow(mbx_ctx *ctx, const mbx_plan *p, int32_t *shallow);
+/* The column-scan kernel class a launch takes (read-only, for tests and
+ * tools: the choice cannot be observed from a scan's results).  Host work
+ * only: nothing is allocated, uploaded or launched. */
+#define MBX_SCAN_COUNT 0
+#define MBX_SCAN_BITSET 1
+#define MBX_SCAN_AGGREGATE 2
+typedef struct {
+  int32_t kernel;      /* 0 k_scan_generic, 1 k_scan_fast */
+  int32_t fast_k, fast_ks; /* k_scan_fast: four-byte slots, 16-byte string slots (0, 0 for k_scan_generic) */
+  int32_t term_body;   /* 0 read from the plan per tile, 1 hoisted compares, 2 int range (IR 1), 3 typed range (IR 2) */
+  int32_t layout;      /* 0 four rows per lane, 1 row-interleaved */
+  int32_t deleted;     /* the DEL instantiation */
+  int32_t sink_lds;    /* BitSet words staged in LDS per block */
+  int32_t fin_mode;    /* 0 write-through partials + ticket, 2 separate fold launch, 3 packed count */
+  int64_t tiles_per_block, blocks;
+} mbx_scan_class;
+/* what mbx_scan_count / mbx_scan_bitmap / mbx_scan_aggregate (mode
+ * MBX_SCAN_COUNT / _BITSET / _AGGREGATE; agg_col -1 unless aggregate, else as
+ * for mbx_scan_aggregate) over the COLUMNS would take now, tuning knobs as
+ * they stand; whether a launch reads planes instead is reported by
+ * mbx_plan_slice_form / mbx_plan_bitmap_form.  term_body and layout are 0 for
+ * k_scan_generic. */
+int mbx_plan_scan_class(mbx_ctx *ctx, const mbx_plan *p, int32_t mode, int32_t agg_col, mbx_scan_class *out);
 
 /* ---- ColumnarFileScan (R/iterator/ColumnarFileScan.java:156-188) --------- */
 /* COUNT of get_next() results: Query.executeFileScan's resultCount. */

@@ -921,13 +921,10 @@ static void str_range_of(KTerm& kt) {
   }
 }
 
-static int plan_variant(mbx_plan* p, int32_t agg_col, PlanVariant** out) {
-  for (auto& v : p->variants)
-    if (v.agg_col == agg_col) {
-      *out = &v;
-      return MBX_OK;
-    }
-  PlanVariant v;
+// The plan with agg_col (-1: none) as the kernels see it: v's class (fast_k,
+// fast_ks, agg_kind) and, when kp is not null, the KPlan to upload.  Host
+// work only.
+static int variant_layout(const mbx_plan* p, int32_t agg_col, PlanVariant& v, KPlan* kp_out) {
   v.agg_col = agg_col;
   KPlan kp = p->host;
   std::vector<int32_t> slots = p->slot_col;
@@ -992,6 +989,25 @@ static int plan_variant(mbx_plan* p, int32_t agg_col, PlanVariant** out) {
         break;
       }
   }
+  if (kp_out) *kp_out = kp;
+  return MBX_OK;
+}
+
+static const PlanVariant* find_variant(const mbx_plan* p, int32_t agg_col) {
+  for (auto& v : p->variants)
+    if (v.agg_col == agg_col) return &v;
+  return nullptr;
+}
+
+static int plan_variant(mbx_plan* p, int32_t agg_col, PlanVariant** out) {
+  if (const PlanVariant* have = find_variant(p, agg_col)) {
+    *out = const_cast<PlanVariant*>(have);
+    return MBX_OK;
+  }
+  PlanVariant v;
+  KPlan kp;
+  int rc = variant_layout(p, agg_col, v, &kp);
+  if (rc) return rc;
   hipError_t e = hipMalloc(&v.dev, sizeof(KPlan));
   if (e == hipSuccess) e = hipMemcpy(v.dev, &kp, sizeof(KPlan), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -1069,27 +1085,23 @@ static ScanGeometry column_geometry(const mbx_plan* p, int64_t tpb) {
   return ScanGeometry{kFormColumns, tpb, grid_blocks(p->t->nrows, tpb)};
 }
 
-static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode, uint64_t* out_words,
-                        Partial* parts, const ScanGeometry& g, int64_t* count_out, AggOut* agg_out,
-                        int32_t* nan_out, const ScanOpts& o = ScanOpts()) {
-  // g.form kFormBytes / kFormBits: g.tpb counts sliced / bit tiles and the launch is the plan's plane scan
-  // (kModeBitmap over bit planes: 256-row tiles, the bitmap's segments)
+// Which kernel class a launch takes: everything of ScanLaunch that follows from
+// the plan, its variant, the mode, the grid and the tuning -- the k_scan_fast
+// instantiation mode_launch / fast_launch / prod_launch pick from it
+// (mbx_scan_mode.hpp; scan_term_body, mbx_internal.hpp) and how the launch is
+// finalized.  Pointers stay the caller's (only o.seg_counts != null is read).
+// The one place these rules live: enqueue_scan launches what it decides and
+// mbx_plan_scan_class reports it.
+static void scan_decide(const mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode,
+                        const ScanGeometry& g, const ScanOpts& o, ScanLaunch& L) {
   const int64_t tpb = g.tpb, nb = g.nb;
-  ScanLaunch L;
-  L.plan = v.dev;
   L.nrows = p->t->nrows;
   L.tiles_per_block = tpb;
   L.deleted = p->t->deleted;
-  L.out_words = out_words;
-  L.partials = parts;
   L.mode = mode;
   L.fast_k = v.fast_k;
   L.fast_ks = v.fast_ks;
   L.agg_kind = v.agg_kind;
-  L.ticket = c->ticket;
-  L.count_out = count_out;
-  L.agg_out = agg_out;
-  L.nan_out = nan_out;
   const MbxTuning& tu = c->tune;
   L.nterms_host = p->host.nterms;
   L.hoist_terms = p->host.nterms >= 1 && p->host.nterms <= kHoistTerms && tu.scan_hoist != 0;
@@ -1103,7 +1115,6 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                          tpb * kWordsPerTile * (int64_t)sizeof(uint64_t) <= kSinkLdsMaxBytes;
   L.sink_lds = sink_fits && (tu.sink_lds == 2 || (tu.sink_lds == 1 && tpb >= 128));
   L.ticket_groups = ticket_groups_of(c);
-  L.seg_counts = o.seg_counts;
   L.words_wt = tu.scan_words_wt;
   L.int_range = 0;
   if (tu.scan_int_range && p->host.nterms >= 1) {
@@ -1139,11 +1150,26 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
   if (!o.need_count && (mode == kModeBitmap || mode == kModeCount) && o.seg_counts && !p->host.has_real &&
       tu.fin_mode < 0)
     L.fin_mode = kFinSegOnly;
-  if (o.frame) {  // mbx_scan_count_frame_async: count_out is the frame
-    L.fin_mode = kFinFrame;
-    L.ticket = nullptr;
-  }
-  if (L.fin_mode == kFinSeparate) L.ticket = nullptr;
+  if (o.frame) L.fin_mode = kFinFrame;  // mbx_scan_count_frame_async: count_out is the frame
+}
+
+static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int32_t mode, uint64_t* out_words,
+                        Partial* parts, const ScanGeometry& g, int64_t* count_out, AggOut* agg_out,
+                        int32_t* nan_out, const ScanOpts& o = ScanOpts()) {
+  // g.form kFormBytes / kFormBits: g.tpb counts sliced / bit tiles and the launch is the plan's plane scan
+  // (kModeBitmap over bit planes: 256-row tiles, the bitmap's segments)
+  const int64_t nb = g.nb;
+  ScanLaunch L;
+  scan_decide(c, p, v, mode, g, o, L);
+  L.plan = v.dev;
+  L.out_words = out_words;
+  L.partials = parts;
+  L.count_out = count_out;
+  L.agg_out = agg_out;
+  L.nan_out = nan_out;
+  L.seg_counts = o.seg_counts;
+  // the count frame and the separate fold take no ticket
+  L.ticket = L.fin_mode == kFinFrame || L.fin_mode == kFinSeparate ? nullptr : c->ticket;
   if (o.fused) {
     int64_t* stamps = nullptr;
     if (c->tune.select_dbg & 8) {  // diagnostic stamps (mbx_diag_select_stamps)
@@ -1456,6 +1482,46 @@ static int scan_agg(mbx_ctx* c, mbx_plan* p, int32_t agg_col, AggOut* dev_out, i
   const ScanGeometry g = column_geometry(p, scan_tiles_per_block(c, p->t->nrows, *v));
   if ((rc = ensure_partials(c, g.nb))) return rc;
   return enqueue_scan(c, p, *v, kModeAgg, nullptr, c->partials, g, nullptr, dev_out, dev_nan);
+}
+
+// What mbx_scan_count / mbx_scan_bitmap / mbx_scan_aggregate would launch over
+// the columns now: their variant (the cached one, else its layout worked out
+// on the host without an upload), their grid, and scan_decide's answer.
+extern "C" int mbx_plan_scan_class(mbx_ctx* c, const mbx_plan* p, int32_t mode, int32_t agg_col, mbx_scan_class* out) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(out);
+  static_assert(MBX_SCAN_COUNT == kModeCount && MBX_SCAN_BITSET == kModeBitmap && MBX_SCAN_AGGREGATE == kModeAgg,
+                "scan modes");
+  if (mode != kModeCount && mode != kModeBitmap && mode != kModeAgg)
+    return fail(MBX_E_INVALID, "plan_scan_class: mode %d", mode);
+  if (mode != kModeAgg && agg_col != -1)
+    return fail(MBX_E_INVALID, "plan_scan_class: agg_col %d without MBX_SCAN_AGGREGATE", agg_col);
+  if (mode == kModeAgg && (agg_col < 0 || agg_col >= (int32_t)p->t->cols.size()))
+    return fail(MBX_E_RANGE, "aggregate: column %d outside 0..%zu", agg_col, p->t->cols.size() - 1);
+  PlanVariant fresh;
+  const PlanVariant* v = find_variant(p, agg_col);
+  if (!v) {
+    int rc = variant_layout(p, agg_col, fresh, nullptr);
+    if (rc) return rc;
+    v = &fresh;
+  }
+  const int64_t nrows = p->t->nrows;
+  const ScanGeometry g =
+      column_geometry(p, mode == kModeBitmap ? tiles_per_block_for(c, nrows) : scan_tiles_per_block(c, nrows, *v));
+  ScanLaunch L;
+  scan_decide(c, p, *v, mode, g, ScanOpts(), L);
+  out->kernel = L.fast_k + L.fast_ks > 0 ? 1 : 0;
+  out->fast_k = L.fast_k;
+  out->fast_ks = L.fast_ks;
+  out->term_body = out->kernel ? scan_term_body(L.fast_ks, mode, L.ri != 0, L.hoist_terms != 0, L.int_range) : 0;
+  out->layout = out->kernel ? L.ri : 0;
+  out->deleted = L.deleted ? 1 : 0;
+  out->sink_lds = L.sink_lds;
+  out->fin_mode = L.fin_mode;
+  out->tiles_per_block = g.tpb;
+  out->blocks = g.nb;
+  return MBX_OK;
 }
 
 extern "C" int mbx_scan_aggregate(mbx_ctx* c, const mbx_plan* pc, int32_t agg_col, mbx_agg* out) {

@@ -164,6 +164,25 @@ struct ScanLaunch {
                                           // BitSet scan (k_scan_bits_words) keeps 256-row tiles
 };
 
+// The term body of a k_scan_fast launch: the instantiation prod_launch<K, KS,
+// MODE, DEL, RI> picks (mbx_scan_mode.hpp switches on this; mbx_plan_scan_class
+// reports it).  hoist_terms / int_range: ScanLaunch's, set by scan_decide
+// (mbx_api.cpp).
+enum TermBody : int32_t {
+  kBodyPlan = 0,        // terms read from the plan per tile (TQ = 0)
+  kBodyHoisted = 1,     // <= kHoistTerms terms in registers, cmp4 per term
+  kBodyIntRange = 2,    // IR = 1: int range tests, hoisted
+  kBodyTypedRange = 3,  // IR = 2: typed range tests, hoisted
+};
+constexpr int32_t scan_term_body(int ks, int mode, bool ri, bool hoist_terms, int int_range) {
+  // int literal terms as branch-free range tests: 4-byte slots only
+  if (ks == 0 && hoist_terms && int_range == 1) return kBodyIntRange;
+  // literal terms of any type as range tests over ordered keys (COUNT /
+  // aggregate scans in the 4-rows-per-lane layout)
+  if (mode != kModeBitmap && !ri && int_range == 2) return kBodyTypedRange;
+  return ks == 0 && hoist_terms ? kBodyHoisted : kBodyPlan;
+}
+
 // ---- byte-plane slices of int32 columns (mbx_table_slice)
 // Key of a value x: k = (uint32)x ^ 0x80000000 (unsigned byte order == signed
 // int order).  Plane p (0 = most significant) holds byte p of every row's key;

@@ -109,26 +109,25 @@ void prod_launch(const ScanLaunch& L, dim3 grid, hipStream_t s) {
                      : (K == 2 && KS == 0 && MODE == kModeCount ? MBX_SCAN_U2
                                                                 : (MODE == kModeAgg ? MBX_SCAN_U_AGG : kDefaultU));
   const unsigned lds = L.sink_lds ? (unsigned)(L.tiles_per_block * kWordsPerTile * sizeof(uint64_t)) : 0u;
-  // int literal terms as branch-free range tests
-  if constexpr (KS == 0) {
-    if (L.hoist_terms && L.int_range == 1) {
-      hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, TQ, RI, 1>), grid, dim3(kBlock), lds, s, L);
+  // the term body (scan_term_body, mbx_internal.hpp); a body the class does
+  // not have is never returned for it, so its case instantiates nothing
+  switch (scan_term_body(KS, MODE, RI, L.hoist_terms != 0, L.int_range)) {
+    case kBodyIntRange:
+      if constexpr (KS == 0)
+        hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, TQ, RI, 1>), grid, dim3(kBlock), lds, s, L);
       return;
-    }
-  }
-  // literal terms of any type as range tests over ordered keys, hoisted
-  // (COUNT / aggregate scans in the 4-rows-per-lane layout)
-  if constexpr (MODE != kModeBitmap && !RI) {
-    if (L.int_range == 2) {
-      hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, kHoistTerms, RI, 2>), grid, dim3(kBlock), lds, s,
-                         L);
+    case kBodyTypedRange:
+      if constexpr (MODE != kModeBitmap && !RI)
+        hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, kHoistTerms, RI, 2>), grid, dim3(kBlock), lds,
+                           s, L);
       return;
-    }
+    case kBodyHoisted:
+      if constexpr (KS == 0)
+        hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, TQ, RI>), grid, dim3(kBlock), lds, s, L);
+      return;
+    default:
+      hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, 0, RI>), grid, dim3(kBlock), lds, s, L);
   }
-  if (KS == 0 && L.hoist_terms)
-    hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, TQ, RI>), grid, dim3(kBlock), lds, s, L);
-  else
-    hipLaunchKernelGGL((k_scan_fast<K, KS, MODE, DEL, kU, kDefaultNT, 0, RI>), grid, dim3(kBlock), lds, s, L);
 }
 
 template <int K, int KS, int MODE>

@@ -25,6 +25,7 @@ STRING, INTEGER, REAL, SYMBOL = 0, 1, 2, 3
 EQ, LT, GT, NE, LE, GE, NOT, NOP, RANGE = range(9)
 IDX_NONE, IDX_BTREE, IDX_HASH, IDX_BITMAP = range(4)
 BM_AND, BM_OR, BM_ANDNOT = range(3)
+SCAN_COUNT, SCAN_BITSET, SCAN_AGGREGATE = range(3)
 E_INVALID, E_TYPE, E_RANGE, E_DEVICE, E_NOMEM, E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 
 
@@ -61,6 +62,14 @@ class Agg(ctypes.Structure):
                 ("fsum", ctypes.c_double), ("fmin", ctypes.c_float), ("fmax", ctypes.c_float)]
 
 
+class ScanClass(ctypes.Structure):
+    """mbx_scan_class (include/mbx.h)."""
+    _fields_ = [("kernel", ctypes.c_int32), ("fast_k", ctypes.c_int32), ("fast_ks", ctypes.c_int32),
+                ("term_body", ctypes.c_int32), ("layout", ctypes.c_int32), ("deleted", ctypes.c_int32),
+                ("sink_lds", ctypes.c_int32), ("fin_mode", ctypes.c_int32),
+                ("tiles_per_block", ctypes.c_int64), ("blocks", ctypes.c_int64)]
+
+
 def java_mutf8(s):
     """DataOutputStream.writeUTF payload bytes of a str (modified UTF-8)."""
     if isinstance(s, (bytes, bytearray)):
@@ -81,7 +90,7 @@ def java_mutf8(s):
 EXPORTS = [
     "mbx_abi_version", "mbx_last_error", "mbx_device_count", "mbx_init", "mbx_free", "mbx_sync", "mbx_stream",
     "mbx_table_stage", "mbx_table_wrap", "mbx_table_free", "mbx_table_info", "mbx_table_group", "mbx_table_slice", "mbx_table_slice_info", "mbx_table_bitslice_info", "mbx_bitslice_range", "mbx_bitslice_bound",
-    "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced", "mbx_plan_slice_form", "mbx_plan_bitmap_form", "mbx_plan_bit_shallow",
+    "mbx_plan_compile", "mbx_plan_free", "mbx_plan_sliced", "mbx_plan_slice_form", "mbx_plan_bitmap_form", "mbx_plan_bit_shallow", "mbx_plan_scan_class",
     "mbx_scan_count", "mbx_scan_count_async", "mbx_scan_count_frame_async", "mbx_count_frame_decode",
     "mbx_count_frame_fits",
     "mbx_scan_blocks", "mbx_scan_bitmap", "mbx_scan_bitmap_async", "mbx_scan_select",
@@ -157,6 +166,7 @@ def lib():
         "mbx_plan_slice_form": ([V, V, P(I32)], ctypes.c_int),
         "mbx_plan_bitmap_form": ([V, V, P(I32)], ctypes.c_int),
         "mbx_plan_bit_shallow": ([V, V, P(I32)], ctypes.c_int),
+        "mbx_plan_scan_class": ([V, V, I32, I32, P(ScanClass)], ctypes.c_int),
         "mbx_table_bitslice_info": ([V, I32, P(I32)], ctypes.c_int),
         "mbx_bitslice_range": ([ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_uint32), P(I32), P(I32)], ctypes.c_int),
         "mbx_bitslice_bound": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, I32, P(I32), P(I32)],
@@ -462,6 +472,14 @@ class Context:
         n = ctypes.c_int32()
         _chk(lib().mbx_plan_bit_shallow(self.h, plan.h, ctypes.byref(n)))
         return n.value
+
+    def plan_scan_class(self, plan, mode, agg_col=-1):
+        """mbx_plan_scan_class: the column-scan kernel class a launch of `mode`
+        (SCAN_COUNT / SCAN_BITSET / SCAN_AGGREGATE) takes now, as a dict of
+        mbx_scan_class's fields."""
+        k = ScanClass()
+        _chk(lib().mbx_plan_scan_class(self.h, plan.h, mode, agg_col, ctypes.byref(k)))
+        return {name: getattr(k, name) for name, _ in ScanClass._fields_}
 
     def bitslice_info(self, table, col):
         """mbx_table_bitslice_info: the bit planes column `col` keeps (0: none)."""

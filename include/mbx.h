@@ -530,12 +530,22 @@ int mbx_comm_allgather_count_all(mbx_comm *const *comms, int32_t n, const int64_
  * replayed with one launch.  Between begin and end the context's *_async
  * calls and its communicator's collectives are recorded, not run; scratch
  * must already be sized by one uncaptured call of the same query (a capture
- * allocates nothing).  Replays run on the context stream. */
+ * allocates nothing).  Replays run on the context stream.
+ * A run of COUNT scans of shallow bit-plane plans (mbx_plan_bit_shallow)
+ * recorded back to back may be replayed as one kernel launch, up to 32 scans
+ * each (tuning knob graph_fuse_counts, default 1, read at mbx_graph_begin; 0:
+ * one kernel node per scan).  Results are unchanged -- every scan is evaluated
+ * in full into the word or frame it was given -- and the order against
+ * everything else recorded is kept: scans share a launch only when nothing
+ * was recorded between them and their outputs do not overlap.
+ * mbx_graph_info: the graph's nodes; how many of them hold more than one
+ * COUNT scan, and the scans in those (any pointer may be null). */
 typedef struct mbx_graph mbx_graph;
 int mbx_graph_begin(mbx_ctx *ctx);
 int mbx_graph_end(mbx_ctx *ctx, mbx_graph **out);
 int mbx_graph_launch(mbx_graph *g);
 int mbx_graph_free(mbx_graph *g);
+int mbx_graph_info(const mbx_graph *g, int64_t *nodes, int64_t *fused_launches, int64_t *fused_scans);
 
 /* ---- device result slots for callers without a HIP allocator of their own
  * (the JNI glue: *_async results and the collectives' buffers live in device
@@ -563,7 +573,8 @@ int mbx_probe_read(mbx_ctx *ctx, const mbx_table *t, const int32_t *cols, int32_
  * "select_blocks", "select_dbg", "cursor_prefetch", "scan_select_fused", "scan_select_waves", "select_flag_stride",
  * "comm_same_stream", "scan_words_wt" (the column scans' BitSet words write-through; the bit-plane BitSet scan
  * does not honour it and always stores plain), "auto_slice", "auto_bitslice" (mbx_plan_compile above),
- * "bits_shallow" (0: every bit-plane plan takes k_scan_bits; read at launch), "bitmap_plane_floor" (rows from which
+ * "bits_shallow" (0: every bit-plane plan takes k_scan_bits; read at launch),
+ * "graph_fuse_counts" (mbx_graph_begin above), "bitmap_plane_floor" (rows from which
  * BitSet launches of a bit-bound plan take the planes, mbx_plan_bitmap_form above; -1: the built-in rule), and the one-launch ColumnarIndexScan's (k_cnf_select) "cnf_lookback" (0 auto,
  * 1 chained, 2 polled), "cnf_flag_stride" (1 or 16), "cnf_blocks" (0: 1024), "cnf_store" (0 default, 1 plain,
  * 2 write-through, 3 nontemporal); "reset" restores the defaults. */

@@ -110,6 +110,7 @@ static void tuning_defaults(MbxTuning& t) {
   t.auto_slice = env_knob("MBX_AUTO_SLICE", 1) != 0;
   t.auto_bitslice = env_knob("MBX_AUTO_BITSLICE", 1) != 0;
   t.bits_shallow = env_knob("MBX_BITS_SHALLOW", 1) != 0;
+  t.graph_fuse_counts = env_knob("MBX_GRAPH_FUSE_COUNTS", 1) != 0;
   t.bitmap_plane_floor = env_knob("MBX_BITMAP_PLANE_FLOOR", -1);
   t.cnf_blocks = (int32_t)env_knob("MBX_CNF_BLOCKS", 0);
   t.cnf_flag_stride = env_knob("MBX_CNF_FLAG_STRIDE", 1) == kFlagStride ? kFlagStride : 1;
@@ -230,13 +231,17 @@ extern "C" int mbx_init(int32_t device, mbx_ctx** out) {
     if (e == hipSuccess) e = hipMalloc(&c->dcount, sizeof(int64_t) * 2);
     if (e == hipSuccess) e = hipMalloc(&c->dnan, sizeof(int32_t) * 4);
     if (e == hipSuccess) e = hipMemset(c->dnan, 0, sizeof(int32_t) * 4);
-    if (e == hipSuccess) e = hipMalloc(&c->ticket, sizeof(uint32_t) * kTicketWords);
-    if (e == hipSuccess) e = hipMemset(c->ticket, 0, sizeof(uint32_t) * kTicketWords);
+    if (e == hipSuccess) e = hipMalloc(&c->ticket, sizeof(uint32_t) * kTicketWords * kMaxFuse);
+    if (e == hipSuccess) e = hipMemset(c->ticket, 0, sizeof(uint32_t) * kTicketWords * kMaxFuse);
     if (e == hipSuccess) e = hipHostMalloc(&c->pinned, 256, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc(&c->lookback, sizeof(int64_t) * kLookbackWords);
     if (e == hipSuccess) e = hipMemset(c->lookback, 0, sizeof(int64_t) * kLookbackWords);
     if (e != hipSuccess) {
       rc = fail(MBX_E_DEVICE, "mbx_init: %s", hipGetErrorString(e));
+      break;
+    }
+    if (!(c->fuse = bits1_fuse_new())) {
+      rc = fail(MBX_E_NOMEM, "mbx_init: host allocation");
       break;
     }
     rc = ensure_partials(c, 4096);
@@ -259,6 +264,7 @@ extern "C" int mbx_free(mbx_ctx* c) {
   hipFree(c->dcount);
   hipFree(c->dnan);
   hipFree(c->ticket);
+  bits1_fuse_free(c->fuse);
   hipFree(c->ids_scratch);
   hipFree(c->stamps);
   hipFree(c->lookback);
@@ -345,6 +351,7 @@ extern "C" int mbx_set_tuning(mbx_ctx* c, const char* knob, int64_t value) {
   else if (!strcmp(knob, "auto_slice")) t.auto_slice = v != 0;
   else if (!strcmp(knob, "auto_bitslice")) t.auto_bitslice = v != 0;
   else if (!strcmp(knob, "bits_shallow")) t.bits_shallow = v != 0;
+  else if (!strcmp(knob, "graph_fuse_counts")) t.graph_fuse_counts = v != 0;
   else if (!strcmp(knob, "bitmap_plane_floor")) t.bitmap_plane_floor = v < 0 ? -1 : v;
   else return fail(MBX_E_INVALID, "mbx_set_tuning: unknown knob `%s`", knob);
   return MBX_OK;
@@ -1180,8 +1187,8 @@ static int enqueue_scan(mbx_ctx* c, const mbx_plan* p, const PlanVariant& v, int
                               c->tune.select_dbg >> 4, c->tune.scan_select_waves, c->tune.select_flag_stride));
     return MBX_OK;
   }
-  if (g.form != kFormColumns)
-    HIPCHK(launch_plane_scan(L, p, g.form, c->stream));
+  if (g.form != kFormColumns)  // a captured COUNT may join the launch recorded before it (Bits1Fuse)
+    HIPCHK(launch_plane_scan(L, p, g.form, c->stream, c->capturing && mode == kModeCount ? c->fuse : nullptr));
   else
     HIPCHK(launch_scan(L, c->stream));
   if (L.fin_mode == kFinSeparate)

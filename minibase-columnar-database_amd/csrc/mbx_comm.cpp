@@ -37,6 +37,8 @@ struct mbx_graph {
   mbx_ctx* ctx = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
+  int64_t nodes = 0;                            // mbx_graph_info
+  int64_t fused_launches = 0, fused_scans = 0;  // the capture's COUNT chains (Bits1Fuse, mbx_planes.hip)
 };
 
 #define NCCLCHK(expr)                                                                             \
@@ -110,8 +112,11 @@ void comm_release(mbx_comm* m) {
 bool same_stream(const mbx_comm* m) { return m->ctx->tune.comm_same_stream != 0; }
 hipStream_t xstream(const mbx_comm* m) { return same_stream(m) ? m->ctx->stream : m->xs; }
 
-// the exchange stream waits for the context stream's work so far
+// the exchange stream waits for the context stream's work so far.  Every collective starts here, so
+// here a captured chain of COUNT scans ends: the collective reads what the scans before it wrote,
+// and a one-rank collective may record no node of its own to end the chain by.
 int fork_after_main(mbx_comm* m) {
+  bits1_fuse_cut(m->ctx->fuse);
   if (same_stream(m)) return MBX_OK;
   HIPCHK(hipEventRecord(m->ev_main, m->ctx->stream));
   HIPCHK(hipStreamWaitEvent(m->xs, m->ev_main, 0));
@@ -247,6 +252,7 @@ extern "C" int mbx_comm_info(const mbx_comm* m, int32_t* nranks, int32_t* rank) 
 extern "C" int mbx_comm_wait(mbx_comm* m) {
   NOTNULL(m);
   HIPCHK(hipSetDevice(m->ctx->device));
+  bits1_fuse_cut(m->ctx->fuse);
   if (same_stream(m)) return MBX_OK;  // already in the context stream's order
   HIPCHK(hipEventRecord(m->ev_x, m->xs));
   HIPCHK(hipStreamWaitEvent(m->ctx->stream, m->ev_x, 0));
@@ -399,6 +405,7 @@ extern "C" int mbx_graph_begin(mbx_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
   c->capturing = true;
+  bits1_fuse_begin(c->fuse, c->tune.graph_fuse_counts != 0);
   return MBX_OK;
 }
 
@@ -409,6 +416,8 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   if (!c->capturing) return fail(MBX_E_INVALID, "graph_end: no capture open");
   HIPCHK(hipSetDevice(c->device));
   c->capturing = false;
+  int64_t fused_launches = 0, fused_scans = 0;
+  bits1_fuse_end(c->fuse, &fused_launches, &fused_scans);  // whatever becomes of the capture, its chain is over
   // the exchange stream's captured work joins the origin stream (a capture
   // ends only with every forked stream joined back); the capture is ended
   // even when the join (or anything captured before it) failed, so the
@@ -431,6 +440,13 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   }
   mg->ctx = c;
   mg->graph = g;
+  mg->fused_launches = fused_launches;
+  mg->fused_scans = fused_scans;
+  size_t nn = 0;
+  if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess)
+    mg->nodes = (int64_t)nn;
+  else
+    (void)hipGetLastError();
   const hipError_t e = hipGraphInstantiate(&mg->exec, g, nullptr, nullptr, 0);
   if (e != hipSuccess) {
     hipGraphDestroy(g);
@@ -445,6 +461,14 @@ extern "C" int mbx_graph_launch(mbx_graph* g) {
   NOTNULL(g);
   HIPCHK(hipSetDevice(g->ctx->device));
   HIPCHK(hipGraphLaunch(g->exec, g->ctx->stream));
+  return MBX_OK;
+}
+
+extern "C" int mbx_graph_info(const mbx_graph* g, int64_t* nodes, int64_t* fused_launches, int64_t* fused_scans) {
+  NOTNULL(g);
+  if (nodes) *nodes = g->nodes;
+  if (fused_launches) *fused_launches = g->fused_launches;
+  if (fused_scans) *fused_scans = g->fused_scans;
   return MBX_OK;
 }
 

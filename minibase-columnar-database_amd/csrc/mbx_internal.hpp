@@ -341,6 +341,9 @@ constexpr int kTicketStride = 32;                 // uint32 per ticket line
 constexpr int kMaxTicketGroups = 64;
 constexpr int kTicketWords = (kMaxTicketGroups + 1) * kTicketStride;
 constexpr int kDefaultTicketGroups = 32;
+// Shallow COUNT scans one captured launch may hold (k_scan_bits1_batch); a context keeps as many
+// ticket areas of kTicketWords, query j of a batch on area j, area 0 every other launch's
+constexpr int kMaxFuse = 32;
 
 enum FinMode : int32_t {
   kFinWriteThrough = 0,  // sc1 partial stores + ticket, sc1 loads by the last block
@@ -523,7 +526,19 @@ hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, 
 // bit-plane COUNT scan: L.bp set, L.tiles_per_block in bit tiles.  shallow: the host copy of a plan
 // with bit_plan_shallow (its launch is k_scan_bits1, which takes what it needs of the plan in its
 // kernel arguments), or null (k_scan_bits, which reads L.bp)
-hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s);
+// fuse: the context's chain of captured shallow COUNT launches while a capture is open and
+// graph_fuse_counts is on, else null.  A k_scan_bits1 launch that may join the chain (bits1_fuse_join's
+// rules) becomes one more grid row of the chain's kernel node instead of a node of its own.
+struct Bits1Fuse;
+hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s, Bits1Fuse* fuse = nullptr);
+// A context's chain state (mbx_planes.hip), allocated once at mbx_init.  begin: a capture opens
+// (on: the graph_fuse_counts knob) -- no chain, counters zeroed; end: the capture is over -- no
+// chain; what the capture fused: launches that hold more than one scan, and the scans in them
+Bits1Fuse* bits1_fuse_new();
+void bits1_fuse_free(Bits1Fuse* f);
+void bits1_fuse_begin(Bits1Fuse* f, bool on);
+void bits1_fuse_cut(Bits1Fuse* f);  // the chain ends here: the next launch starts a new one (a collective)
+void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans);
 // bit-plane BitSet scan (k_scan_bits_words): L.bp set; the grid is the output bitmap's, so
 // L.tiles_per_block keeps its 256-row meaning (a segment of tiles_per_block x 4 words); writes
 // every word of L.out_words and L.seg_counts[block].  L.words_wt is not honoured: plain stores

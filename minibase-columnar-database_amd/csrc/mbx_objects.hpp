@@ -78,6 +78,9 @@ struct MbxTuning {
                                   // bit planes binds to those (k_scan_bits); 0: every sliced plan takes the byte planes
   int32_t bits_shallow = 1;       // MBX_BITS_SHALLOW: a bit-plane plan whose every term has depth <= 1 takes
                                   // k_scan_bits1 (read at launch); 0: every bit-plane plan takes k_scan_bits
+  int32_t graph_fuse_counts = 1;  // MBX_GRAPH_FUSE_COUNTS: a run of shallow bit-plane COUNT scans recorded back to back
+                                  // in a graph capture is one launch (k_scan_bits1_batch; read at mbx_graph_begin);
+                                  // 0: one kernel node per scan
   int64_t bitmap_plane_floor = -1; // MBX_BITMAP_PLANE_FLOOR: rows from which BitSet launches of a bit-bound plan take the
                                   // planes (k_scan_bits_words; read at launch).  -1: shallow plans always, deep plans from
                                   // 2^25 rows and <= 8 planes per column (mbx_planes.cpp); 0: every bit-bound plan
@@ -97,7 +100,9 @@ struct mbx_ctx {
   AggOut* dagg = nullptr;
   int64_t* dcount = nullptr;
   int32_t* dnan = nullptr;       // async scans: [0] last, [1] sticky until mbx_sync; sync scans: [2]
-  uint32_t* ticket = nullptr;   // in-launch finalize ticket (always 0 between launches)
+  uint32_t* ticket = nullptr;   // in-launch finalize tickets (always 0 between launches): kMaxFuse areas of
+                                // kTicketWords; every launch takes area 0, query j of a fused batch area j
+  mbx::Bits1Fuse* fuse = nullptr;  // chain of captured shallow COUNT launches (mbx_planes.hip), owned
   int64_t* ids_scratch = nullptr;  // positions for a gather whose caller wants no positions
   int64_t ids_cap = 0;
   int64_t* stamps = nullptr;    // diagnostic per-block stamps (select_dbg bit 3)
@@ -271,7 +276,8 @@ bool plan_has_real(const mbx_plan* p);
 void bind_planes(mbx_ctx* c, mbx_plan* p);
 ScanGeometry count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tpb);
 ScanGeometry bitmap_geometry(const mbx_plan* p, int64_t tpb);
-hipError_t launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s);
+hipError_t launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s,
+                             Bits1Fuse* fuse = nullptr);
 // mbx_comm.cpp: mbx_sync / mbx_free of a context with a communicator
 int comm_sync(mbx_ctx* c);
 void comm_release_of(mbx_ctx* c);

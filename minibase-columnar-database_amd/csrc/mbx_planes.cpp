@@ -396,11 +396,11 @@ static bool takes_shallow(const mbx_plan* p) {
   return p->ctx->tune.bits_shallow != 0 && bit_plan_shallow(p->planes.bits);
 }
 
-hipError_t mbx::launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s) {
+hipError_t mbx::launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s, Bits1Fuse* fuse) {
   if (form == kFormBits) {
     L.bp = (const KBitPlan*)p->planes.dev;
     if (L.mode == kModeBitmap) return launch_scan_bits_words(L, s);
-    return launch_scan_bits(L, takes_shallow(p) ? &p->planes.bits : nullptr, s);
+    return launch_scan_bits(L, takes_shallow(p) ? &p->planes.bits : nullptr, s, fuse);
   }
   if (L.mode != kModeCount) return hipErrorInvalidValue;  // the byte planes answer COUNT only
   L.sl = (const KSlicePlan*)p->planes.dev;

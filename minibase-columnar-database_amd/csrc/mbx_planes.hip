@@ -4,6 +4,7 @@
 // build the planes.  The scans answer what ColumnarFileScan.get_next
 // (R/iterator/ColumnarFileScan.java:156-172) counts, or which rows it returns,
 // reading only the bytes or bits of each row that decide the predicate.
+#include <new>
 #include <type_traits>
 
 #include "mbx_device.hpp"
@@ -733,103 +734,44 @@ __device__ __forceinline__ v4u bit_tile_load(const uint32_t* p, int lane) {
 // (rows < 2^40, and the host holds tiles_per_block to the table's tiles), so
 // the segment bounds and the loop's compares are 32-bit scalar arithmetic.
 // FIN: kPlaneFinPacked or kPlaneFinFrame.
+// The body is mbx_scan_bits1_body.hpp, the text of both kernels over the record P.  As a __device__
+// function that both call it cost this kernel 4 to 14 instructions per instantiation (hipcc reduces
+// the tile loop's induction differently after inlining); included, its code is what it was.
 template <int NP, bool DEL, int FIN>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_bits1(Bits1Launch P) {
-  constexpr int kB = bits1_batch(NP, DEL);
-  constexpr int kNP = NP > 0 ? NP : 1, kC = 1 << (kNP - 1);
-  constexpr int kTileDwords = kBitTileRows / 32;
-  // The epilogue's arguments, held in scalar registers from here on: left alone, hipcc loads them
-  // after the block's barrier, a scalar memory round trip between the last plane load and the
-  // block's atomic.  Here they ride in the one round of argument loads before the first plane load.
-  uint64_t out = reinterpret_cast<uint64_t>(P.out), ticket = reinterpret_cast<uint64_t>(P.ticket);
-  uint64_t nan_out = reinterpret_cast<uint64_t>(P.nan_out);
-  int32_t groups = P.ticket_groups;
-  uint32_t nblocks = gridDim.x;
-  if constexpr (FIN == kPlaneFinPacked)
-    asm volatile("" : "+s"(out), "+s"(ticket), "+s"(nan_out), "+s"(groups), "+s"(nblocks));
-  else
-    asm volatile("" : "+s"(out));
-  const int lane = threadIdx.x & 63;
-  const int wave = (int)uniform(threadIdx.x >> 6);
-  const int tp = (int)(P.nrows / kBitTileRows);     // the full tiles = the partial tile's number
-  const int prows = (int)(P.nrows % kBitTileRows);  // the partial tile's rows
-  const int t0 = (int)blockIdx.x * P.tiles_per_block;
-  const int t1 = min(t0 + P.tiles_per_block, tp + (prows != 0 ? 1 : 0));
-  const uint32_t* pl[kNP];
-#pragma unroll
-  for (int k = 0; k < kNP; ++k) pl[k] = P.pl[k];
-  uint32_t la[kC], lb[kC];  // uniform: bits1_rows' leaves
-#pragma unroll
-  for (int c = 0; c < kC; ++c) {
-    const uint32_t f0 = (P.table >> (2 * c)) & 1u, f1 = (P.table >> (2 * c + 1)) & 1u;
-    lb[c] = f0 ? ~0u : 0u;
-    la[c] = f0 != f1 ? ~0u : 0u;
-  }
-  gu32* del = (gu32*)P.deleted;
-  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(P.deleted) & 15) == 0;  // uniform
+#define MBX_BITS1_GRID_X gridDim.x
+#include "mbx_scan_bits1_body.hpp"
+#undef MBX_BITS1_GRID_X
+}
 
-  uint32_t cnt = 0;
-  const int tf = min(t1, tp);  // full tiles in the main loop
-  for (int base = min(t0 + wave, tf); base < tf; base += kWaves * kB) {
-    v4u x[kB][kNP], dead[kB];
-    // every load of the batch, unconditional; a tile past the full tiles is the last one again, and is not counted
-    int64_t dw[kB];  // the tile's first dword in every plane (uniform)
-#pragma unroll
-    for (int u = 0; u < kB; ++u) {
-      dw[u] = (int64_t)min(base + u * kWaves, tf - 1) * kTileDwords;
-      x[u][0] = bit_splat(0u);
-#pragma unroll
-      for (int k = 0; k < NP; ++k) x[u][k] = bit_tile_load(pl[k] + dw[u], lane);
-    }
-    if (DEL) {
-      if (del16) {
-#pragma unroll
-        for (int u = 0; u < kB; ++u) dead[u] = bit_tile_load(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
-      } else {
-#pragma unroll
-        for (int u = 0; u < kB; ++u) {
-          gu32* d = (gu32*)bit_tile_lane(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) dead[u][i] = d[i];
-        }
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);  // no use of a loaded tile is scheduled among the loads: one wait, after the last
+// A run of independent shallow COUNT scans recorded back to back in a graph
+// capture, as one launch (Bits1Fuse below): grid row y is query y, its record
+// picked from the kernel arguments by a scalar index, and runs k_scan_bits1's
+// body as it stands -- blockIdx.x, the query's blocks and its own ticket area
+// are what a launch of its own would see.  Blocks are dispatched x-fastest, so
+// a query's tail and finalize run under the next query's loads, and the run
+// pays one launch's ramp and drain.  Every query of a batch is the same
+// instantiation over the same number of blocks, nb.  A grid row is nb rounded
+// up to the chip's 8 XCDs (the padding blocks leave at once): workgroups go to
+// the XCDs round-robin in dispatch order, so block x of every row runs on XCD
+// x % 8 as in a launch of its own, and queries over the same planes find their
+// segments in the L2 that read them last.
+constexpr unsigned kXcds = 8;
+struct Bits1Batch {
+  Bits1Launch q[kMaxFuse];
+  uint32_t nb;  // blocks per query
+  uint32_t pad_;
+};
+static_assert(sizeof(Bits1Launch) == 88, "k_scan_bits1's kernel arguments");
+static_assert(sizeof(Bits1Batch) == kMaxFuse * 88 + 8 && sizeof(Bits1Batch) <= 4096, "a batch fits the kernel arguments");
 
-#pragma unroll
-    for (int u = 0; u < kB; ++u) {
-      uint32_t c = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        uint32_t xi[kNP];
-#pragma unroll
-        for (int k = 0; k < kNP; ++k) xi[k] = x[u][k][i];
-        const uint32_t rows = bits1_rows<NP>(xi, la, lb);
-        c += (uint32_t)__popc(DEL ? rows & ~dead[u][i] : rows);
-      }
-      cnt += base + u * kWaves < tf ? c : 0u;
-    }
-  }
-  // the partial tile, owned like any other tile of [t0, t1)
-  if (prows != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
-    v4u xp[kNP];
-    xp[0] = bit_splat(0u);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) xp[k] = bit_tile_load(pl[k] + (int64_t)tp * kTileDwords, lane);
-    const int64_t dw = (int64_t)tp * kTileDwords + lane * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int rem = prows - (lane * 4 + i) * 32;  // the dword's rows below nrows
-      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
-      if (DEL && rem > 0) valid &= ~del[dw + i];
-      uint32_t xi[kNP];
-#pragma unroll
-      for (int k = 0; k < kNP; ++k) xi[k] = xp[k][i];
-      cnt += (uint32_t)__popc(bits1_rows<NP>(xi, la, lb) & valid);
-    }
-  }
-  plane_count_finish<FIN>(cnt, reinterpret_cast<int64_t*>(out), reinterpret_cast<uint32_t*>(ticket), groups,
-                          reinterpret_cast<int32_t*>(nan_out), nblocks);
+template <int NP, bool DEL, int FIN>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_scan_bits1_batch(Bits1Batch B) {
+  if (blockIdx.x >= B.nb) return;
+  const Bits1Launch& P = B.q[blockIdx.y];
+#define MBX_BITS1_GRID_X B.nb
+#include "mbx_scan_bits1_body.hpp"
+#undef MBX_BITS1_GRID_X
 }
 
 // planes 0..w-1 of 64 rows per wave step: one ballot per plane, lane j stores
@@ -870,8 +812,126 @@ static int plane_fin_of(const ScanLaunch& L) {
   return kPlaneFinGeneral;
 }
 
+// ---- chains of captured shallow COUNT launches (launch_scan_bits' `fuse`)
+//
+// While a capture is open the context keeps the last k_scan_bits1 launch it recorded: its graph
+// node, its instantiation and grid, and the launch records of the chain so far.  The next such
+// launch joins the chain -- no node is added, the chain's node becomes k_scan_bits1_batch over one
+// more grid row -- when nothing else was recorded in between (the stream's capture dependencies are
+// still exactly that node), it is the same instantiation over the same number of blocks, the batch
+// has room and its output overlaps no output of the batch.  The queries of a batch run concurrently:
+// they read planes nothing in the batch writes, write distinct words and arrive on ticket areas of
+// their own, so each result is what its own launch gives; everything else recorded keeps its order
+// against the whole batch.  The graph stays linear.  A graph call that fails leaves the nodes as
+// they are and ends fusion on the context for good: a capture never fails because of a chain.
+struct Bits1Fuse {
+  bool on = false;      // the open capture fuses
+  bool broken = false;  // a graph call failed on this context
+  hipGraphNode_t node = nullptr;  // the chain's kernel node, the capture's tail when it was recorded; null: no chain
+  int key = 0;          // bits1_key of the chain's instantiation
+  unsigned gx = 0;      // its blocks per query
+  int n = 0;            // its queries
+  int64_t launches = 0, scans = 0;  // this capture: nodes that hold more than one query, the queries in them
+  Bits1Batch B;
+};
+
+Bits1Fuse* bits1_fuse_new() { return new (std::nothrow) Bits1Fuse(); }
+void bits1_fuse_free(Bits1Fuse* f) { delete f; }
+void bits1_fuse_begin(Bits1Fuse* f, bool on) {
+  f->on = on && !f->broken;
+  f->node = nullptr;
+  f->n = 0;
+  f->launches = f->scans = 0;
+}
+void bits1_fuse_cut(Bits1Fuse* f) {
+  f->node = nullptr;
+  f->n = 0;
+}
+void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans) {
+  if (fused_launches) *fused_launches = f->launches;
+  if (fused_scans) *fused_scans = f->scans;
+  f->on = false;
+  f->node = nullptr;
+  f->n = 0;
+}
+
+constexpr int bits1_key(int np, bool del, int fin) { return np * 4 + (del ? 2 : 0) + (fin == kPlaneFinFrame ? 1 : 0); }
+
+static void bits1_fuse_break(Bits1Fuse* f) {
+  (void)hipGetLastError();
+  f->broken = true;
+  f->on = false;
+  f->node = nullptr;
+}
+
+// the stream's only capture dependency, or null (none, several, or not capturing)
+static hipGraphNode_t bits1_capture_tail(Bits1Fuse* f, hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  const hipGraphNode_t* deps = nullptr;
+  size_t nd = 0;
+  if (hipStreamGetCaptureInfo_v2(s, &st, nullptr, nullptr, &deps, &nd) != hipSuccess) {
+    bits1_fuse_break(f);
+    return nullptr;
+  }
+  return st == hipStreamCaptureStatusActive && nd == 1 && deps ? deps[0] : nullptr;
+}
+
+// the launch just recorded starts a chain of one: today's single kernel node
+static void bits1_fuse_start(Bits1Fuse* f, const Bits1Launch& P, int key, dim3 grid, hipStream_t s) {
+  f->node = nullptr;
+  hipGraphNode_t tail = bits1_capture_tail(f, s);
+  hipGraphNodeType ty = hipGraphNodeTypeEmpty;
+  if (!tail || hipGraphNodeGetType(tail, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) return;
+  f->node = tail;
+  f->key = key;
+  f->gx = grid.x;
+  f->n = 1;
+  f->B.q[0] = P;
+}
+
+// true: P is grid row f->n of the chain's node now and needs no launch
+template <int NP, bool DEL, int FIN>
+static bool bits1_fuse_join(Bits1Fuse* f, Bits1Launch P, dim3 grid, hipStream_t s) {
+  if (!f->node || f->key != bits1_key(NP, DEL, FIN) || f->gx != grid.x || f->n >= kMaxFuse) return false;
+  // the count word, or the whole count frame
+  const uintptr_t bytes = FIN == kPlaneFinFrame ? sizeof(int64_t) * kFrameSlots * kFrameSlotStride : sizeof(int64_t);
+  const uintptr_t o = reinterpret_cast<uintptr_t>(P.out);
+  for (int j = 0; j < f->n; ++j) {
+    const uintptr_t q = reinterpret_cast<uintptr_t>(f->B.q[j].out);
+    if (o < q + bytes && q < o + bytes) return false;
+  }
+  const hipGraphNode_t tail = bits1_capture_tail(f, s);
+  if (!tail || tail != f->node) return false;  // something else was recorded since (or the call failed)
+  if (FIN == kPlaneFinPacked) P.ticket += (size_t)f->n * kTicketWords;
+  f->B.q[f->n] = P;
+  void* args[1] = {&f->B};
+  hipKernelNodeParams kp{};
+  kp.func = reinterpret_cast<void*>(&k_scan_bits1_batch<NP, DEL, FIN>);
+  f->B.nb = f->gx;
+  kp.gridDim = dim3((f->gx + kXcds - 1) / kXcds * kXcds, (unsigned)(f->n + 1));
+  kp.blockDim = dim3(kBlock);
+  kp.sharedMemBytes = 0;
+  kp.kernelParams = args;
+  kp.extra = nullptr;
+  if (hipGraphKernelNodeSetParams(f->node, &kp) != hipSuccess) {
+    bits1_fuse_break(f);  // the node is what it was: the chain so far
+    return false;
+  }
+  f->n += 1;
+  f->launches += f->n == 2 ? 1 : 0;
+  f->scans += f->n == 2 ? 2 : 1;
+  return true;
+}
+
+template <int NP, bool DEL, int FIN>
+static void bits1_launch_del(const Bits1Launch& P, dim3 grid, hipStream_t s, Bits1Fuse* fuse) {
+  if (fuse && bits1_fuse_join<NP, DEL, FIN>(fuse, P, grid, s)) return;
+  hipLaunchKernelGGL((k_scan_bits1<NP, DEL, FIN>), grid, dim3(kBlock), 0, s, P);
+  if (fuse && fuse->on) bits1_fuse_start(fuse, P, bits1_key(NP, DEL, FIN), grid, s);
+}
+
 template <int NP, int FIN>
-static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
+static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s, Bits1Fuse* fuse) {
   Bits1Launch P = bits1_plan_of(B);
   const int64_t ntiles = (L.nrows + kBitTileRows - 1) / kBitTileRows;
   P.nrows = L.nrows;
@@ -882,19 +942,19 @@ static void bits1_launch(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipS
   P.nan_out = L.nan_out;
   P.ticket_groups = L.ticket_groups;
   if (L.deleted)
-    hipLaunchKernelGGL((k_scan_bits1<NP, true, FIN>), grid, dim3(kBlock), 0, s, P);
+    bits1_launch_del<NP, true, FIN>(P, grid, s, fuse);
   else
-    hipLaunchKernelGGL((k_scan_bits1<NP, false, FIN>), grid, dim3(kBlock), 0, s, P);
+    bits1_launch_del<NP, false, FIN>(P, grid, s, fuse);
 }
 
 template <int FIN>
-static hipError_t bits1_launch_np(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s) {
+static hipError_t bits1_launch_np(const ScanLaunch& L, const KBitPlan& B, dim3 grid, hipStream_t s, Bits1Fuse* fuse) {
   switch (bit_plan_reads(B)) {  // one plane per term that reads
-    case 0: bits1_launch<0, FIN>(L, B, grid, s); break;
-    case 1: bits1_launch<1, FIN>(L, B, grid, s); break;
-    case 2: bits1_launch<2, FIN>(L, B, grid, s); break;
-    case 3: bits1_launch<3, FIN>(L, B, grid, s); break;
-    case 4: bits1_launch<4, FIN>(L, B, grid, s); break;
+    case 0: bits1_launch<0, FIN>(L, B, grid, s, fuse); break;
+    case 1: bits1_launch<1, FIN>(L, B, grid, s, fuse); break;
+    case 2: bits1_launch<2, FIN>(L, B, grid, s, fuse); break;
+    case 3: bits1_launch<3, FIN>(L, B, grid, s, fuse); break;
+    case 4: bits1_launch<4, FIN>(L, B, grid, s, fuse); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -912,14 +972,18 @@ static hipError_t bits_launch(const ScanLaunch& L, dim3 grid, hipStream_t s) {
 // shallow: the plan's host copy when its launch is k_scan_bits1's.  That kernel
 // exists in the two hot forms only; a shallow plan's launch in the general form
 // is k_scan_bits', which takes every bit plan (L.bp).
-hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s) {
+hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s, Bits1Fuse* fuse) {
   const dim3 grid((unsigned)blocks_for(L.nrows, kBitTileRows, L.tiles_per_block));
   const int fin = plane_fin_of(L);
   if (shallow && !bit_plan_shallow(*shallow)) return hipErrorInvalidValue;
+  if (fuse && !fuse->on) fuse = nullptr;
+  // every other kernel ends a chain by being recorded: the capture's tail is its node then
   if (fin == kPlaneFinGeneral) return bits_launch<kPlaneFinGeneral>(L, grid, s);
   if (fin == kPlaneFinFrame)
-    return shallow ? bits1_launch_np<kPlaneFinFrame>(L, *shallow, grid, s) : bits_launch<kPlaneFinFrame>(L, grid, s);
-  return shallow ? bits1_launch_np<kPlaneFinPacked>(L, *shallow, grid, s) : bits_launch<kPlaneFinPacked>(L, grid, s);
+    return shallow ? bits1_launch_np<kPlaneFinFrame>(L, *shallow, grid, s, fuse)
+                   : bits_launch<kPlaneFinFrame>(L, grid, s);
+  return shallow ? bits1_launch_np<kPlaneFinPacked>(L, *shallow, grid, s, fuse)
+                 : bits_launch<kPlaneFinPacked>(L, grid, s);
 }
 
 hipError_t launch_scan_bits_words(const ScanLaunch& L, hipStream_t s) {

@@ -84,8 +84,10 @@ struct MbxTuning {
   int64_t bitmap_plane_floor = -1; // MBX_BITMAP_PLANE_FLOOR: rows from which BitSet launches of a bit-bound plan take the
                                   // planes (k_scan_bits_words; read at launch).  -1: shallow plans always, deep plans from
                                   // 2^25 rows and <= 8 planes per column (mbx_planes.cpp); 0: every bit-bound plan
-  int32_t select_dbg = 0;        // MBX_SELECT_DBG: bit 3 per-block stamps, 128 every-predecessor poll
-                                  // instead of the chained look-back, 512 write-through flip; -DMBX_DIAG
+  int32_t select_dbg = 0;        // MBX_SELECT_DBG: bit 3 per-block stamps; 128 flips a launcher's look-back
+                                  // choice -- k_cnf_select polls every predecessor where it would walk the
+                                  // chain, k_scan_select walks the chain instead of polling; 512
+                                  // write-through flip; -DMBX_DIAG
                                   // builds only: k_select_ids bit 0 no prefix / bit 1 no emission, the
                                   // one-launch selections' 16 back-off / 32 no wait / 64 plain-load polls
 };

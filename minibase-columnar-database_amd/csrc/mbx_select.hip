@@ -254,8 +254,9 @@ __global__ __launch_bounds__(64 * NW) void k_cnf_select(BitmapCnf C, const uint6
 // i-th tile go to lanes 4i..4i+3 of register i / 16), stores them as the
 // BitSet (coalesced, after its loads) with the block's segment count, then
 // select_tail turns them into positions: count published, offset from the
-// predecessors (chained look-back), leading steps staged before the offset
-// is known -- no second launch, no re-read of the BitSet.  Plans of 1..4
+// predecessors (every predecessor polled; select_dbg bit 7: the chained
+// walk), leading steps staged before the offset is known -- no second
+// launch, no re-read of the BitSet.  Plans of 1..4
 // 4-byte int literal terms (no float compare: no NaN reach), wave ranges of
 // <= kSelRegs x 16 tiles (tables up to ~134 M rows), <= kLookbackBlocks blocks.
 template <int K, bool DEL, int U, int TQ, int NW, int NR, int IR = 0>
@@ -498,8 +499,11 @@ hipError_t launch_cnf_materialize(const BitmapCnf& c, const uint64_t* deleted, i
   // 46.6-48.0.  So (lookback 0, auto) narrow projections read from column
   // groups -- and positions-only launches -- poll, the rest walk the chain;
   // inclusive prefixes are 32-bit, so tables of >= 2^32 rows always poll.
-  // lookback 1 / 2 (tuning cnf_lookback) force the chain / the polls, as
-  // select_dbg bit 7 (MBX_SELECT_DBG=128) forces the polls.
+  // lookback 1 / 2 (tuning cnf_lookback) force the chain / the polls.
+  // select_dbg bit 7 (128; bit 3 of the dbg passed in) forces the polls here
+  // whatever cnf_lookback says -- the opposite of launch_scan_select, where
+  // the same bit selects the chained walk -- so a test picks this kernel's
+  // form with cnf_lookback and k_scan_select's with select_dbg.
   bool grouped = narrow;
   for (int j = 0; j < nproj; ++j) grouped = grouped && proj[j].gstride > 0;
   const bool chained = nbits < (int64_t(1) << 32) && !(dbg & 8) &&
@@ -561,8 +565,9 @@ hipError_t launch_scan_select(const ScanLaunch& L, int64_t* lb, int64_t row_offs
   // 15 waves), one flag per 128-byte line (flag_stride kFlagStride, the
   // default: the polls of all blocks do not queue on a few lines) -- C2
   // 11.8-12.1 us vs 13.4-13.6 for the chained walk and 12.0-12.2 with the
-  // flags packed (profiles/r04/f1); select_dbg bit 7: the chained walk
-  // (32-bit inclusive prefixes: tables < 2^32 rows)
+  // flags packed (profiles/r04/f1); select_dbg bit 7 (bit 3 of the dbg
+  // passed in): the chained walk (32-bit inclusive prefixes: tables < 2^32
+  // rows).  In launch_cnf_materialize the same bit forces the polls.
   const int32_t fs = (dbg & 8) || flag_stride != kFlagStride ? 1 : kFlagStride;
   const bool del = L.deleted != nullptr;
   const bool ir = L.int_range != 0;  // branch-free int terms (every fused plan qualifies; the knob can turn it off)

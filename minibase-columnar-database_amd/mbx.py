@@ -751,6 +751,15 @@ class Context:
                                    ctypes.byref(n)))
         return ids[:n.value], [o[:n.value] for o in outs]
 
+    def materialize_async(self, table, bitmap, proj, dev_ids, dev_outs, dev_count):
+        """mbx_materialize_async: positions + projected rows of a BitSet's
+        selection into device buffers (device pointers as ints; dev_ids None:
+        positions stay in context scratch; dev_outs[j] in the device row layout
+        of column proj[j]; dev_count None: the count stays in the context)."""
+        pj = (ctypes.c_int32 * max(1, len(proj)))(*proj)
+        outs = (ctypes.c_void_p * max(1, len(proj)))(*dev_outs)
+        _chk(lib().mbx_materialize_async(self.h, table.h, bitmap.h, pj, len(proj), dev_ids, outs, dev_count))
+
     def cursor(self, table, bitmap, proj):
         h = ctypes.c_void_p()
         pj = (ctypes.c_int32 * max(1, len(proj)))(*proj)

@@ -1,5 +1,5 @@
 // mbx_internal.hpp -- device-side plan layout and kernel launchers shared by
-// the C-ABI layer (mbx_api.cpp, mbx_planes.cpp) and the CDNA4 kernels (mbx_*.hip).
+// the C-ABI layer (mbx_api.cpp and a host file per family, mbx_*.cpp) and the CDNA4 kernels (mbx_*.hip).
 //
 // HBM layout (DESIGN.md "Data layout"):
 //   * int32 / float32 column: nrows contiguous 4-byte values, position order.
@@ -167,7 +167,7 @@ struct ScanLaunch {
 // The term body of a k_scan_fast launch: the instantiation prod_launch<K, KS,
 // MODE, DEL, RI> picks (mbx_scan_mode.hpp switches on this; mbx_plan_scan_class
 // reports it).  hoist_terms / int_range: ScanLaunch's, set by scan_decide
-// (mbx_api.cpp).
+// (mbx_scan.cpp).
 enum TermBody : int32_t {
   kBodyPlan = 0,        // terms read from the plan per tile (TQ = 0)
   kBodyHoisted = 1,     // <= kHoistTerms terms in registers, cmp4 per term

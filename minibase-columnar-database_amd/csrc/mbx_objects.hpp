@@ -1,6 +1,7 @@
 // mbx_objects.hpp -- host-side objects behind the opaque handles of
-// include/mbx.h and include/mbx_db.h, shared by mbx_api.cpp (scans, bitmaps,
-// cursors) and mbx_db.cpp (Minibase DB files).  Not part of the C-ABI.
+// include/mbx.h and include/mbx_db.h, shared by the C-ABI's files (mbx_api.cpp,
+// mbx_table.cpp, mbx_plan.cpp, mbx_scan.cpp, mbx_bitmap.cpp, mbx_cursor.cpp)
+// and mbx_db.cpp (Minibase DB files).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -93,6 +94,19 @@ struct MbxTuning {
 };
 constexpr int64_t kMaxStampBlocks = 65536;
 
+// The context's pinned host scratch: where the synchronous entry points read
+// back what a launch left on the device.  One member per use, so no two
+// copies in flight in one call share a word.
+struct HostScratch {
+  int64_t count;         // a scan's / BitSet's count (scan_result_sync, bitmap_count_sync)
+  AggOut agg;            // mbx_scan_aggregate's result
+  int32_t scan_nan;      // dnan[2] after a synchronous COUNT / BitSet scan (check_nan)
+  int32_t agg_nan;       // dnan[2] after mbx_scan_aggregate
+  int32_t sticky_nan;    // dnan[1], the asynchronous scans' sticky word (mbx_sync)
+  int64_t cursor_count;  // a launched CNF cursor's pending count (cursor_resolve)
+};
+static_assert(sizeof(HostScratch) <= 256, "the pinned scratch is 256 bytes");
+
 struct mbx_ctx {
   int32_t device = 0;
   MbxTuning tune;
@@ -109,7 +123,7 @@ struct mbx_ctx {
   int64_t ids_cap = 0;
   int64_t* stamps = nullptr;    // diagnostic per-block stamps (select_dbg bit 3)
   int64_t* lookback = nullptr;  // k_cnf_select's epoch + per-block counts (kLookbackWords, zeroed once)
-  void* pinned = nullptr;       // 256 bytes of pinned host scratch
+  HostScratch* pinned = nullptr;  // 256 bytes of pinned host scratch
   mbx_comm* comm = nullptr;     // multi-GPU exchange (mbx_comm.cpp), owned
   bool capturing = false;       // mbx_graph_begin .. mbx_graph_end
 };
@@ -196,7 +210,9 @@ struct mbx_plan {
   std::vector<int32_t> slot_col;  // table column of each slot
   bool all_literal = true;        // every term is `column OP literal`
   bool str_lit_fits16 = true;     // every string literal is <= 16 bytes
-  std::deque<PlanVariant> variants;
+  // one per aggregate column scanned so far, uploaded on demand by the scan
+  // entry points (which take a const plan): owned
+  mutable std::deque<PlanVariant> variants;
   PlaneBinding planes;  // set by mbx::bind_planes; dev is owned
 };
 
@@ -242,6 +258,27 @@ struct mbx_cursor {
 namespace mbx {
 
 int set_device(mbx_ctx* c);
+// c->partials holds at least n
+int ensure_partials(mbx_ctx* c, int64_t n);
+// *out = the diagnostic per-block stamps (allocated at first use) when tuning
+// select_dbg bit 3 is set, else null
+int stamps_of(mbx_ctx* c, int64_t** out);
+// tiles per segment of a BitSet over nrows rows (mbx_scan.cpp)
+int64_t tiles_per_block_for(const mbx_ctx* c, int64_t nrows);
+int col_kind(int32_t attr);
+// mbx_plan.cpp.  variant_layout: the plan with agg_col (-1: none) as the
+// kernels see it, host work only; find_variant: the uploaded one, or null;
+// plan_variant: the uploaded one, uploading it first when missing
+int variant_layout(const mbx_plan* p, int32_t agg_col, PlanVariant& v, KPlan* kp_out);
+const PlanVariant* find_variant(const mbx_plan* p, int32_t agg_col);
+int plan_variant(const mbx_plan* p, int32_t agg_col, const PlanVariant** out);
+// mbx_bitmap.cpp: checks a CNF over bitmaps of nbits bits and fills *C
+int cnf_args(int64_t nbits, const mbx_bitmap* const* bms, const int32_t* conj_offsets, int32_t nconj,
+             const mbx_bitmap* deleted, BitmapCnf* C);
+// mbx_cursor.cpp: positions (dev_ids, null: context scratch) and projected rows
+// of a bitmap's set bits, one launch; dev_total null: c->dcount + 1
+int materialize_dev(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, const int32_t* proj, int32_t nproj,
+                    int64_t row_offset, int64_t* dev_ids, void* const* dev_out, int64_t* dev_total);
 int32_t stride_words(const mbx_col_desc& d);
 int check_cols(const mbx_col_desc* cols, int32_t ncols);
 int64_t words_for(int64_t nbits);

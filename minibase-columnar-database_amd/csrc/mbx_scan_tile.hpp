@@ -79,7 +79,7 @@ __device__ __forceinline__ void str16_accept4(const uint32_t (&rows)[4][4], uint
 // bound checks -- only the one partial tile needs them
 // IR = 1: every term is an int `column OP literal` (ScanLaunch.int_range): the
 // term body is one unsigned range test per row, no branch on the operator or
-// the comparison type (KTerm.rlo / rspan / rneg, mbx_api.cpp int_range_of).
+// the comparison type (KTerm.rlo / rspan / rneg, mbx_plan.cpp int_range_of).
 // IR = 2: literal terms of any type, one range test over a signed-ordered key
 // (KTerm.rm31: float bits; a char(16) term's compareTo sign); a float term
 // still tracks PredEval's NaN reach

@@ -22,9 +22,25 @@
  *                 the inner relation per block); within a pass inner
  *                 ascending, then outer ascending within the block.
  *
- * The pair matrix is computed by k_join_matrix (one wave per 64 pairs, the
- * wave ballot is one word of the matrix row), then compacted with the scan's
- * nextSetBit kernels; results stay in HBM until fetched.
+ * Two forms compute the same pairs, in the same order, with the same pass
+ * numbers and errors:
+ *
+ *   MBX_JOIN_FORM_MATRIX  the pair matrix, O(no * ni): k_join_matrix (one wave
+ *                 per 64 pairs, the wave ballot is one word of the matrix row),
+ *                 compacted with the scan's nextSetBit kernels.  Every CNF.
+ *   MBX_JOIN_FORM_EQUI    for a CNF with an equality key (mbx_join_equi_conj),
+ *                 O((no + ni) log + candidates): the build side is sorted by
+ *                 the key (the stable radix sort of mbx_sort.h), every probe
+ *                 row finds its run of equal keys by binary search, and the
+ *                 runs are expanded into candidate pairs on which the rest of
+ *                 the CNF is evaluated.  BMJ probes with the outer selection
+ *                 and NLJ with the inner one, so the candidates are born
+ *                 outer-major / inner-major; NLJ with more than one pass is
+ *                 then stably sorted by pass alone (the pass is monotone in
+ *                 the outer index, so stability keeps inner, then outer,
+ *                 ascending within a pass).
+ *
+ * Results stay in HBM until fetched.
  */
 #ifndef MBX_JOIN_H
 #define MBX_JOIN_H
@@ -68,6 +84,49 @@ typedef struct mbx_join_cnf {
 int mbx_join(mbx_ctx* ctx, const mbx_table* outer, const mbx_bitmap* outer_sel, const mbx_table* inner,
              const mbx_bitmap* inner_sel, const mbx_join_cnf* cnf, int32_t order, int64_t outer_block,
              mbx_join_result** out);
+
+/* The conjunct mbx_join_with can use as an equality key, or -1: the first
+ * conjunct that is exactly one term with op aopEQ whose two columns are both
+ * attrInteger or both attrString, provided no term of an EARLIER conjunct is
+ * on attrReal columns.  PredEval evaluates the conjuncts in order and stops at
+ * the first false one: a float compare after the key is reached only on pairs
+ * whose keys are equal -- the candidates the equi form evaluates -- but one
+ * before it is reached on every pair, and its NaN must raise even where no
+ * key matches.  outer_attr / inner_attr: the AttrType of each table column.
+ * A malformed CNF (null pointers, more than 32 conjuncts or MBX_MAX_JOIN_TERMS
+ * terms, decreasing offsets, a column outside the tables, a term on columns of
+ * two types) gives -1 here and keeps failing in mbx_join.  No GPU is used. */
+int32_t mbx_join_equi_conj(const mbx_join_cnf* cnf, const int32_t* outer_attr, int32_t nouter,
+                           const int32_t* inner_attr, int32_t ninner);
+
+#define MBX_JOIN_FORM_AUTO 0   /* EQUI iff the CNF has a key and outer selected * inner selected >= 2^30 */
+#define MBX_JOIN_FORM_MATRIX 1 /* always works */
+#define MBX_JOIN_FORM_EQUI 2   /* MBX_E_UNSUPPORTED where mbx_join_equi_conj gives -1 */
+
+/* form: MBX_JOIN_FORM_*.  chunk_pairs: the candidate pairs the equi form
+ * handles per round (its BitSet scratch); 0 = the default 2^30, the pair
+ * matrix's 128 MiB bound; larger values clamp to it, so it only ever lowers
+ * (tests place chunk boundaries inside small joins with it). */
+typedef struct mbx_join_opts {
+  int32_t form;
+  int32_t pad_;
+  int64_t chunk_pairs;
+} mbx_join_opts;
+
+/* mbx_join with options; opts == NULL: MBX_JOIN_FORM_AUTO and the default
+ * chunk, which is what mbx_join passes.  AUTO's floor of 2^30 pairs is one full
+ * chunk of the pair matrix: from there the matrix form pays a host round trip
+ * per chunk.  The equi form keeps a uint32 permutation of the result for the
+ * NLJ pass sort and a uint32 row per build-side row: more than 2^32 - 1 result
+ * pairs with more than one pass, or a build-side table of more than 2^31 - 1
+ * rows, is MBX_E_UNSUPPORTED under MBX_JOIN_FORM_EQUI, and AUTO takes the
+ * matrix form. */
+int mbx_join_with(mbx_ctx* ctx, const mbx_table* outer, const mbx_bitmap* outer_sel, const mbx_table* inner,
+                  const mbx_bitmap* inner_sel, const mbx_join_cnf* cnf, int32_t order, int64_t outer_block,
+                  const mbx_join_opts* opts, mbx_join_result** out);
+
+/* the form that produced the result: MBX_JOIN_FORM_MATRIX or MBX_JOIN_FORM_EQUI */
+int mbx_join_result_form(const mbx_join_result* r, int32_t* form);
 
 /* number of result pairs; number of passes over the inner relation (NLJ:
  * ceil(outer selected / outer_block), at least 1; BMJ: 1) */

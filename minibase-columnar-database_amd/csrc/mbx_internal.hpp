@@ -484,6 +484,60 @@ hipError_t launch_join_decode(const int64_t* ids, const int64_t* n, int64_t max_
 hipError_t launch_gather_pos(const int64_t* pos, int64_t n, int64_t row_offset, const void* col, int32_t stride_w,
                              void* out, hipStream_t s);
 
+// The equi form (MBX_JOIN_FORM_EQUI).  The probe side is the selection whose
+// order leads the output (BMJ: outer, NLJ: inner), the build side the other
+// one, as `perm`: its rows sorted by the key, ties by ascending row.  Probe row
+// i matches the build slots [lo[i], lo[i] + cnt[i]); candidate c of the join
+// is slot lo[i] + c - off[i] of the probe row i with off[i] <= c < off[i + 1].
+struct JoinEqui {
+  int32_t key_kind;              // kInt / kStr
+  int32_t probe_outer;           // 1: BMJ, 0: NLJ
+  int32_t pstride_w, bstride_w;  // words per row of the two key columns
+  const void* pcol;              // probe key column (table-local rows)
+  const void* bcol;              // build key column
+  const int64_t* ppos;           // probe selection: rows, ascending
+  int64_t np;
+  const uint32_t* perm;          // build rows in key order
+  int64_t nb;
+  const int32_t* skeys;          // int key: bcol[perm[j]], contiguous for the search
+  uint32_t* lo;                  // np
+  int64_t* cnt;                  // np
+  int64_t* off;                  // np + 1: exclusive scan of cnt, off[np] = candidates
+  int64_t np_top, nb_top;        // the largest power of two <= np / nb (0 for none): the searches' first step
+};
+
+struct JoinEquiOut {
+  const uint32_t* brank;  // NLJ with passes > 1: index of perm[j] in the outer selection; else null (pass 0)
+  int64_t block;          // NLJ outer block
+  int64_t outer_offset, inner_offset;
+  int64_t base;           // output index of the first pair of this chunk
+  int64_t* out_outer;
+  int64_t* out_inner;
+  int32_t* out_pass;
+};
+
+constexpr int64_t kJoinScanBlocks = 1024;  // segments of k_join_scan_*; bsum holds as many int64
+
+// skeys[j] = col[perm[j]]
+hipError_t launch_join_gather_keys(const uint32_t* perm, int64_t n, const int32_t* col, int32_t* skeys, hipStream_t s);
+// brank[j] = the index of perm[j] in pos[0 .. npos) (ascending; every perm[j] is in it)
+hipError_t launch_join_rank(const uint32_t* perm, int64_t n, const int64_t* pos, int64_t npos, uint32_t* brank,
+                            hipStream_t s);
+// E.lo, E.cnt
+hipError_t launch_join_probe(const JoinEqui& E, hipStream_t s);
+// E.off from E.cnt; *total = off[np] (device); bsum: kJoinScanBlocks int64 of scratch
+hipError_t launch_join_scan(const JoinEqui& E, int64_t* bsum, int64_t* total, hipStream_t s);
+// candidates [c0, c0 + nc): bit k of out = the CNF holds on candidate c0 + k (whole words; sets A.nan)
+hipError_t launch_join_expand(const JoinArgs& A, const JoinEqui& E, int64_t c0, int64_t nc, uint64_t* out,
+                              hipStream_t s);
+// pair k of the chunk = candidate c0 + ids[k] (ids null: c0 + k), k < n
+hipError_t launch_join_equi_decode(const JoinEqui& E, const JoinEquiOut& D, const int64_t* ids, int64_t c0, int64_t n,
+                                   hipStream_t s);
+// out[k] = in[perm[k]] for the three result arrays
+hipError_t launch_join_permute(const uint32_t* perm, int64_t n, const int64_t* in_outer, const int64_t* in_inner,
+                               const int32_t* in_pass, int64_t* out_outer, int64_t* out_inner, int32_t* out_pass,
+                               hipStream_t s);
+
 // read-bandwidth probe (k_read_probe): the scan's loads without a predicate
 constexpr int kMaxProbeCols = 4;
 struct ProbeArgs {

@@ -35,6 +35,8 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // ----------------------------------------------------------------- objects
 
+struct mbx_sort_key;  // include/mbx_sort.h
+
 using mbx::AggOut;
 using mbx::KPlan;
 using mbx::Partial;
@@ -317,6 +319,14 @@ ScanGeometry count_geometry(const mbx_ctx* c, const mbx_plan* p, int64_t tpb);
 ScanGeometry bitmap_geometry(const mbx_plan* p, int64_t tpb);
 hipError_t launch_plane_scan(ScanLaunch& L, const mbx_plan* p, int32_t form, hipStream_t s,
                              Bits1Fuse* fuse = nullptr);
+// mbx_sort.hip.  sort_perm: mbx_sort (its validation, errors and passes) with
+// the sorted permutation of table-local rows left on the device -- *perm is the
+// caller's to hipFree, null when *n is 0; sort_by_i32: a stable ascending sort
+// of the indices 0 .. n-1 (1 <= n <= 2^32 - 1) by the device array vals[index]
+int sort_perm(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, const mbx_sort_key* keys, int32_t nkeys,
+              int32_t order, int32_t run_pages, uint32_t** perm, int64_t* n, int32_t* passes_run,
+              int32_t* passes_total);
+int sort_by_i32(mbx_ctx* c, const int32_t* vals, int64_t n, uint32_t** perm);
 // mbx_comm.cpp: mbx_sync / mbx_free of a context with a communicator
 int comm_sync(mbx_ctx* c);
 void comm_release_of(mbx_ctx* c);

@@ -21,6 +21,9 @@
 // first, char(n) as the bytes of the device string image in memory order
 // (mbx_internal.hpp "HBM layout": byte b of row r is byte b of the modified
 // UTF-8 payload, so byte order is String.compareTo order); DSC complements it.
+// The equi join (mbx_join.cpp) uses the same passes twice, through sort_perm
+// (mbx_sort with the permutation left on the device) and sort_by_i32 (indices
+// ordered by an int32 device array: its pairs by pass).
 #include "../../include/mbx_sort.h"
 
 #include <hip/hip_runtime.h>
@@ -279,6 +282,61 @@ __global__ __launch_bounds__(kBlock) void k_sort_scatter(SortDigit D, const uint
 
 int64_t grid_for(int64_t n) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 4 * kResidentBlocks)); }
 
+// blocks of the per-digit passes over n rows
+struct SortGrid {
+  int64_t tiles_per_block, nblocks;
+};
+SortGrid sort_grid(int64_t n) {
+  const int64_t ntiles = (n + kSortTile - 1) / kSortTile;
+  SortGrid g;
+  g.tiles_per_block = (ntiles + kSortMaxBlocks - 1) / kSortMaxBlocks;
+  g.nblocks = (ntiles + g.tiles_per_block - 1) / g.tiles_per_block;
+  return g;
+}
+
+// The histograms of every digit in one read of the key words (H.cols, nwords
+// words per row; H.rows / H.n / H.hist are set here), one host sync, then the
+// passes over digits[ndigits - 1 .. 0] that do not leave every row in one bin.
+// pa holds the initial permutation (rows_in_perm: of rows in any order, else
+// the identity); *sorted = pa or pb.  hist: ndigits * 256 words, counts:
+// nblocks * 256 words.
+hipError_t sort_passes(SortHistArgs& H, const std::vector<SortDigit>& digits, int32_t nwords, int64_t n,
+                       bool rows_in_perm, uint32_t* pa, uint32_t* pb, uint32_t* hist, uint32_t* counts,
+                       hipStream_t s, uint32_t** sorted, int32_t* passes_run) {
+  const int32_t ndigits = (int32_t)digits.size();
+  const SortGrid g = sort_grid(n);
+  std::vector<uint32_t> hhist((size_t)ndigits * kRadix);
+  hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * hhist.size(), s);
+  if (e == hipSuccess) {
+    H.rows = rows_in_perm ? pa : nullptr;
+    H.n = n;
+    H.hist = hist;
+    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kResidentBlocks));
+    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)gx, (unsigned)nwords), dim3(kBlock), 0, s, H);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(hhist.data(), hist, sizeof(uint32_t) * hhist.size(), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the one sync: which passes run
+  uint32_t *src = pa, *dst = pb;
+  for (int32_t q = ndigits - 1; q >= 0 && e == hipSuccess; --q) {
+    const uint32_t* hq = hhist.data() + (size_t)q * kRadix;
+    bool skip = false;
+    for (int b = 0; b < kRadix; ++b) skip = skip || hq[b] == (uint32_t)n;
+    if (skip) continue;  // one bin holds every row: the pass would not move anything
+    hipLaunchKernelGGL(k_sort_count, dim3((unsigned)g.nblocks), dim3(kBlock), 0, s, digits[(size_t)q], src, n,
+                       g.tiles_per_block, counts);
+    hipLaunchKernelGGL(k_sort_scan, dim3(kRadix), dim3(kBlock), 0, s, hist + (size_t)q * kRadix, counts, g.nblocks);
+    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)g.nblocks), dim3(kBlock), 0, s, digits[(size_t)q], src, n,
+                       g.tiles_per_block, counts, dst);
+    e = hipGetLastError();
+    std::swap(src, dst);
+    ++*passes_run;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  *sorted = src;
+  return e;
+}
+
 }  // namespace
 
 struct mbx_sort_result {
@@ -290,13 +348,15 @@ struct mbx_sort_result {
   ~mbx_sort_result() { hipFree(perm); }
 };
 
-extern "C" int mbx_sort(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, const mbx_sort_key* keys, int32_t nkeys,
-                        int32_t order, int32_t run_pages, mbx_sort_result** out) {
-  NOTNULL(c);
-  NOTNULL(t);
-  NOTNULL(keys);
-  NOTNULL(out);
-  *out = nullptr;
+// mbx_sort's validation and passes; the sorted permutation (table-local rows)
+// stays on the device: *perm (hipFree; null when *n == 0)
+int mbx::sort_perm(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, const mbx_sort_key* keys, int32_t nkeys,
+                   int32_t order, int32_t run_pages, uint32_t** perm, int64_t* n_out, int32_t* passes_run,
+                   int32_t* passes_total) {
+  *perm = nullptr;
+  *n_out = 0;
+  *passes_run = 0;
+  *passes_total = 0;
   if (nkeys < 1) return fail(MBX_E_INVALID, "sort: No target columns given.");
   if (nkeys > MBX_MAX_PRED_COLS) return fail(MBX_E_UNSUPPORTED, "sort: %d sort columns (max %d)", nkeys, MBX_MAX_PRED_COLS);
   if (order != MBX_SORT_ASC && order != MBX_SORT_DSC)
@@ -356,33 +416,22 @@ extern "C" int mbx_sort(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, c
   int rc = set_device(c);
   if (rc) return rc;
   hipStream_t s = c->stream;
-  mbx_sort_result* r = new (std::nothrow) mbx_sort_result();
-  if (!r) return fail(MBX_E_NOMEM, "sort: host allocation");
-  r->row_offset = t->row_offset;
-  r->passes_total = ndigits;
+  *passes_total = ndigits;
   int64_t n = t->nrows;
   if (sel) {
-    if ((rc = ensure_count(c, const_cast<mbx_bitmap*>(sel)))) {
-      delete r;
-      return rc;
-    }
+    if ((rc = ensure_count(c, const_cast<mbx_bitmap*>(sel)))) return rc;
     n = sel->count;
   }
-  r->count = n;
-  if (n == 0) {
-    *out = r;
-    return MBX_OK;
-  }
+  *n_out = n;
+  if (n == 0) return MBX_OK;
 
-  const int64_t ntiles = (n + kSortTile - 1) / kSortTile;
-  const int64_t tiles_per_block = (ntiles + kSortMaxBlocks - 1) / kSortMaxBlocks;
-  const int64_t nblocks = (ntiles + tiles_per_block - 1) / tiles_per_block;
+  const SortGrid g = sort_grid(n);
   uint32_t *pa = nullptr, *pb = nullptr, *hist = nullptr, *counts = nullptr;
   int64_t* ids = nullptr;
   hipError_t e = hipMalloc(&pa, sizeof(uint32_t) * (size_t)n);
   if (e == hipSuccess) e = hipMalloc(&pb, sizeof(uint32_t) * (size_t)n);
   if (e == hipSuccess) e = hipMalloc(&hist, sizeof(uint32_t) * (size_t)ndigits * kRadix);
-  if (e == hipSuccess) e = hipMalloc(&counts, sizeof(uint32_t) * (size_t)nblocks * kRadix);
+  if (e == hipSuccess) e = hipMalloc(&counts, sizeof(uint32_t) * (size_t)g.nblocks * kRadix);
   if (e == hipSuccess && sel) e = hipMalloc(&ids, sizeof(int64_t) * (size_t)n);
   auto release = [&]() {
     hipFree(pa);
@@ -393,7 +442,6 @@ extern "C" int mbx_sort(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, c
   };
   if (e != hipSuccess) {
     release();
-    delete r;
     return fail(MBX_E_NOMEM, "sort: scratch for %lld rows: %s", (long long)n, hipGetErrorString(e));
   }
 
@@ -409,43 +457,80 @@ extern "C" int mbx_sort(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, c
                        (int64_t)run_pages);
     e = hipGetLastError();
   }
-  // every digit's histogram in one read of the key columns
-  std::vector<uint32_t> hhist((size_t)ndigits * kRadix);
-  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * hhist.size(), s);
-  if (e == hipSuccess) {
-    H.rows = sel ? pa : nullptr;
-    H.n = n;
-    H.hist = hist;
-    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kResidentBlocks));
-    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)gx, (unsigned)nwords), dim3(kBlock), 0, s, H);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(hhist.data(), hist, sizeof(uint32_t) * hhist.size(), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the one sync: which passes run
-  uint32_t *src = pa, *dst = pb;
-  for (int32_t q = ndigits - 1; q >= 0 && e == hipSuccess; --q) {
-    const uint32_t* hq = hhist.data() + (size_t)q * kRadix;
-    bool skip = false;
-    for (int b = 0; b < kRadix; ++b) skip = skip || hq[b] == (uint32_t)n;
-    if (skip) continue;  // one bin holds every row: the pass would not move anything
-    hipLaunchKernelGGL(k_sort_count, dim3((unsigned)nblocks), dim3(kBlock), 0, s, digits[(size_t)q], src, n,
-                       tiles_per_block, counts);
-    hipLaunchKernelGGL(k_sort_scan, dim3(kRadix), dim3(kBlock), 0, s, hist + (size_t)q * kRadix, counts, nblocks);
-    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)nblocks), dim3(kBlock), 0, s, digits[(size_t)q], src, n,
-                       tiles_per_block, counts, dst);
-    e = hipGetLastError();
-    std::swap(src, dst);
-    r->passes_run++;
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  uint32_t* src = nullptr;
+  if (e == hipSuccess) e = sort_passes(H, digits, nwords, n, sel != nullptr, pa, pb, hist, counts, s, &src, passes_run);
   if (e != hipSuccess) {
     release();
-    delete r;
     return fail(MBX_E_DEVICE, "sort: %s", hipGetErrorString(e));
   }
-  r->perm = src;
+  *perm = src;
   (src == pa ? pa : pb) = nullptr;
   release();
+  return MBX_OK;
+}
+
+// A stable ascending sort of the indices 0 .. n-1 (n >= 1, at most 2^32 - 1) by
+// vals[index], a device array of int32 values: an int32 key column of n rows
+// that is not a table's -- the same digits, histograms and passes.  *perm:
+// device, hipFree.
+int mbx::sort_by_i32(mbx_ctx* c, const int32_t* vals, int64_t n, uint32_t** perm) {
+  *perm = nullptr;
+  SortHistArgs H;
+  memset(&H, 0, sizeof(H));
+  H.cols[0].base = (const uint32_t*)vals;
+  H.cols[0].stride_w = 1;
+  H.cols[0].is_int = 1;
+  H.ncols = 1;
+  std::vector<SortDigit> digits;
+  for (int32_t b = 0; b < 4; ++b) digits.push_back(SortDigit{(const uint32_t*)vals, 1, 0, 0x80000000u, 8 * (3 - b), 0u});
+  hipStream_t s = c->stream;
+  const SortGrid g = sort_grid(n);
+  uint32_t *pa = nullptr, *pb = nullptr, *hist = nullptr, *counts = nullptr;
+  hipError_t e = hipMalloc(&pa, sizeof(uint32_t) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&pb, sizeof(uint32_t) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&hist, sizeof(uint32_t) * 4 * kRadix);
+  if (e == hipSuccess) e = hipMalloc(&counts, sizeof(uint32_t) * (size_t)g.nblocks * kRadix);
+  auto release = [&]() {
+    hipFree(pa);
+    hipFree(pb);
+    hipFree(hist);
+    hipFree(counts);
+  };
+  if (e != hipSuccess) {
+    release();
+    return fail(MBX_E_NOMEM, "sort: scratch for %lld values: %s", (long long)n, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(k_sort_init, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, pa, n, (int64_t)0, (int64_t)0);
+  e = hipGetLastError();
+  uint32_t* src = nullptr;
+  int32_t passes_run = 0;
+  if (e == hipSuccess) e = sort_passes(H, digits, 1, n, false, pa, pb, hist, counts, s, &src, &passes_run);
+  if (e != hipSuccess) {
+    release();
+    return fail(MBX_E_DEVICE, "sort: %s", hipGetErrorString(e));
+  }
+  *perm = src;
+  (src == pa ? pa : pb) = nullptr;
+  release();
+  return MBX_OK;
+}
+
+extern "C" int mbx_sort(mbx_ctx* c, const mbx_table* t, const mbx_bitmap* sel, const mbx_sort_key* keys, int32_t nkeys,
+                        int32_t order, int32_t run_pages, mbx_sort_result** out) {
+  NOTNULL(c);
+  NOTNULL(t);
+  NOTNULL(keys);
+  NOTNULL(out);
+  *out = nullptr;
+  mbx_sort_result* r = new (std::nothrow) mbx_sort_result();
+  if (!r) return fail(MBX_E_NOMEM, "sort: host allocation");
+  r->row_offset = t->row_offset;
+  const int rc = sort_perm(c, t, sel, keys, nkeys, order, run_pages, &r->perm, &r->count, &r->passes_run,
+                           &r->passes_total);
+  if (rc) {
+    delete r;
+    return rc;
+  }
   *out = r;
   return MBX_OK;
 }

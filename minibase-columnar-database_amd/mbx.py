@@ -114,10 +114,12 @@ EXPORTS = [
     "mbx_db_purge", "mbx_db_stage_range", "mbx_db_bitmap_stage_range",
     # include/mbx_join.h
     "mbx_join", "mbx_join_info", "mbx_join_fetch", "mbx_join_free", "mbx_gather",
+    "mbx_join_equi_conj", "mbx_join_with", "mbx_join_result_form",
     # include/mbx_sort.h
     "mbx_sort", "mbx_sort_info", "mbx_sort_fetch", "mbx_sort_free",
 ]
 JOIN_BMJ, JOIN_NLJ = 0, 1
+JOIN_FORM_AUTO, JOIN_FORM_MATRIX, JOIN_FORM_EQUI = 0, 1, 2
 SORT_ASC, SORT_DSC = 0, 1
 
 
@@ -133,6 +135,38 @@ class SortKey(ctypes.Structure):
 class JoinCnf(ctypes.Structure):
     _fields_ = [("terms", ctypes.POINTER(JoinTerm)), ("conj_offsets", ctypes.POINTER(ctypes.c_int32)),
                 ("nconj", ctypes.c_int32)]
+
+
+
+class JoinOpts(ctypes.Structure):
+    _fields_ = [("form", ctypes.c_int32), ("pad_", ctypes.c_int32), ("chunk_pairs", ctypes.c_int64)]
+
+
+def make_join_cnf(cnf, keep):
+    """[[(op, outer_col, inner_col), ...], ...] -> JoinCnf (its arrays appended to keep)"""
+    terms = [t for conj in cnf for t in conj]
+    tarr = (JoinTerm * max(1, len(terms)))()
+    for k, (op, a, b) in enumerate(terms):
+        tarr[k].op, tarr[k].outer_col, tarr[k].inner_col = op, a, b
+    offs, o = [0], 0
+    for conj in cnf:
+        o += len(conj)
+        offs.append(o)
+    oarr = (ctypes.c_int32 * len(offs))(*offs)
+    keep += [tarr, oarr]
+    return JoinCnf(tarr, oarr, len(cnf))
+
+
+def join_equi_conj(cnf, outer_attr, inner_attr):
+    """mbx_join_equi_conj: the conjunct of cnf the equi form of the join can
+    use as its key, or -1; outer_attr / inner_attr: each column's AttrType.
+    Needs no GPU."""
+    keep = []
+    c = make_join_cnf(cnf, keep)
+    oa = (ctypes.c_int32 * max(1, len(outer_attr)))(*outer_attr)
+    ia = (ctypes.c_int32 * max(1, len(inner_attr)))(*inner_attr)
+    return lib().mbx_join_equi_conj(ctypes.byref(c), oa, len(outer_attr), ia, len(inner_attr))
+
 
 _lib = None
 
@@ -256,6 +290,9 @@ def lib():
         "mbx_db_stage_range": ([V, V, ctypes.c_char_p, I64, I64, P(V)], ctypes.c_int),
         "mbx_db_bitmap_stage_range": ([V, V, ctypes.c_char_p, I64, I64, P(V)], ctypes.c_int),
         "mbx_join": ([V, V, V, V, V, P(JoinCnf), I32, I64, P(V)], ctypes.c_int),
+        "mbx_join_with": ([V, V, V, V, V, P(JoinCnf), I32, I64, P(JoinOpts), P(V)], ctypes.c_int),
+        "mbx_join_equi_conj": ([P(JoinCnf), P(I32), I32, P(I32), I32], ctypes.c_int32),
+        "mbx_join_result_form": ([V, P(I32)], ctypes.c_int),
         "mbx_join_info": ([V, P(I64), P(I64)], ctypes.c_int),
         "mbx_join_fetch": ([V, V, I64, I64, V, V, V], ctypes.c_int),
         "mbx_join_free": ([V], ctypes.c_int),
@@ -488,31 +525,33 @@ class Context:
         _chk(lib().mbx_table_bitslice_info(table.h, col, ctypes.byref(n)))
         return n.value
 
-    def join(self, outer, outer_sel, inner, inner_sel, cnf, order, outer_block=0):
+    def join(self, outer, outer_sel, inner, inner_sel, cnf, order, outer_block=0, form=0, chunk_pairs=0,
+             info=False):
         """mbx_join: cnf = [[(op, outer_col, inner_col), ...], ...] (0-based
-        columns); returns (outer positions, inner positions, passes) in the
-        reference's order."""
-        terms = [t for conj in cnf for t in conj]
-        tarr = (JoinTerm * max(1, len(terms)))()
-        for k, (op, a, b) in enumerate(terms):
-            tarr[k].op, tarr[k].outer_col, tarr[k].inner_col = op, a, b
-        offs, o = [0], 0
-        for conj in cnf:
-            o += len(conj)
-            offs.append(o)
-        oarr = (ctypes.c_int32 * len(offs))(*offs)
-        c = JoinCnf(tarr, oarr, len(cnf))
+        columns); returns (outer positions, inner positions, pass, passes) in
+        the reference's order.  form (JOIN_FORM_*) / chunk_pairs: mbx_join_with's
+        options; with neither, plain mbx_join is called.  info=True: the form
+        that ran (mbx_join_result_form) as a fifth value."""
+        keep = []
+        c = make_join_cnf(cnf, keep)
         h = ctypes.c_void_p()
-        _chk(lib().mbx_join(self.h, outer.h, outer_sel.h, inner.h, inner_sel.h, ctypes.byref(c), order, outer_block,
-                            ctypes.byref(h)))
+        if form == 0 and chunk_pairs == 0:
+            _chk(lib().mbx_join(self.h, outer.h, outer_sel.h, inner.h, inner_sel.h, ctypes.byref(c), order,
+                                outer_block, ctypes.byref(h)))
+        else:
+            opts = JoinOpts(form, 0, chunk_pairs)
+            _chk(lib().mbx_join_with(self.h, outer.h, outer_sel.h, inner.h, inner_sel.h, ctypes.byref(c), order,
+                                     outer_block, ctypes.byref(opts), ctypes.byref(h)))
         try:
-            n, p = ctypes.c_int64(), ctypes.c_int64()
+            n, p, f = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
             _chk(lib().mbx_join_info(h, ctypes.byref(n), ctypes.byref(p)))
+            _chk(lib().mbx_join_result_form(h, ctypes.byref(f)))
             op_ = np.zeros(max(1, n.value), dtype=np.int64)
             ip_ = np.zeros(max(1, n.value), dtype=np.int64)
             ps = np.zeros(max(1, n.value), dtype=np.int32)
             _chk(lib().mbx_join_fetch(self.h, h, 0, n.value, op_.ctypes.data, ip_.ctypes.data, ps.ctypes.data))
-            return op_[:n.value], ip_[:n.value], ps[:n.value], p.value
+            res = (op_[:n.value], ip_[:n.value], ps[:n.value], p.value)
+            return res + (f.value,) if info else res
         finally:
             lib().mbx_join_free(h)
 

@@ -539,13 +539,19 @@ int mbx_comm_allgather_count_all(mbx_comm *const *comms, int32_t n, const int64_
  * everything else recorded is kept: scans share a launch only when nothing
  * was recorded between them and their outputs do not overlap.
  * mbx_graph_info: the graph's nodes; how many of them hold more than one
- * COUNT scan, and the scans in those (any pointer may be null). */
+ * COUNT scan, and the scans in those (any pointer may be null).
+ * Scans of such a launch that read the same planes (the same plane of the same
+ * columns term for term, the same deleted image) form a plane group: the launch
+ * reads a group's planes once and every member's count comes out of that pass.
+ * mbx_graph_plane_groups: the plane groups over the graph's launches that hold
+ * more than one scan, and the scans in groups of more than one. */
 typedef struct mbx_graph mbx_graph;
 int mbx_graph_begin(mbx_ctx *ctx);
 int mbx_graph_end(mbx_ctx *ctx, mbx_graph **out);
 int mbx_graph_launch(mbx_graph *g);
 int mbx_graph_free(mbx_graph *g);
 int mbx_graph_info(const mbx_graph *g, int64_t *nodes, int64_t *fused_launches, int64_t *fused_scans);
+int mbx_graph_plane_groups(const mbx_graph *g, int64_t *groups, int64_t *shared_scans);
 
 /* ---- device result slots for callers without a HIP allocator of their own
  * (the JNI glue: *_async results and the collectives' buffers live in device

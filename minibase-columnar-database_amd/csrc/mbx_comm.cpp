@@ -39,6 +39,7 @@ struct mbx_graph {
   hipGraphExec_t exec = nullptr;
   int64_t nodes = 0;                            // mbx_graph_info
   int64_t fused_launches = 0, fused_scans = 0;  // the capture's COUNT chains (Bits1Fuse, mbx_planes.hip)
+  int64_t plane_groups = 0, shared_scans = 0;   // mbx_graph_plane_groups
 };
 
 #define NCCLCHK(expr)                                                                             \
@@ -416,8 +417,8 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   if (!c->capturing) return fail(MBX_E_INVALID, "graph_end: no capture open");
   HIPCHK(hipSetDevice(c->device));
   c->capturing = false;
-  int64_t fused_launches = 0, fused_scans = 0;
-  bits1_fuse_end(c->fuse, &fused_launches, &fused_scans);  // whatever becomes of the capture, its chain is over
+  int64_t fused_launches = 0, fused_scans = 0, plane_groups = 0, shared_scans = 0;
+  bits1_fuse_end(c->fuse, &fused_launches, &fused_scans, &plane_groups, &shared_scans);  // whatever becomes of the capture, its chain is over
   // the exchange stream's captured work joins the origin stream (a capture
   // ends only with every forked stream joined back); the capture is ended
   // even when the join (or anything captured before it) failed, so the
@@ -442,6 +443,8 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   mg->graph = g;
   mg->fused_launches = fused_launches;
   mg->fused_scans = fused_scans;
+  mg->plane_groups = plane_groups;
+  mg->shared_scans = shared_scans;
   size_t nn = 0;
   if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess)
     mg->nodes = (int64_t)nn;
@@ -469,6 +472,13 @@ extern "C" int mbx_graph_info(const mbx_graph* g, int64_t* nodes, int64_t* fused
   if (nodes) *nodes = g->nodes;
   if (fused_launches) *fused_launches = g->fused_launches;
   if (fused_scans) *fused_scans = g->fused_scans;
+  return MBX_OK;
+}
+
+extern "C" int mbx_graph_plane_groups(const mbx_graph* g, int64_t* groups, int64_t* shared_scans) {
+  NOTNULL(g);
+  if (groups) *groups = g->plane_groups;
+  if (shared_scans) *shared_scans = g->shared_scans;
   return MBX_OK;
 }
 

@@ -774,6 +774,207 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #undef MBX_BITS1_GRID_X
 }
 
+// Queries of a chain that read the same planes (same pl[0..NP), deleted image,
+// rows and segment: a *plane group*) differ only in their truth table, and
+// every such query's COUNT is a sum of the same 2^NP minterm populations
+//   m_i = popcount(live & AND_k (bit k of i ? x_k : ~x_k)),  count_q = sum of m_i over the set bits i of table_q.
+// k_scan_bits1_shared reads a group's planes once: grid row y is group y, the
+// loop is k_scan_bits1's (tile ownership, kB loads per wave before the first
+// wait, scalar tile addresses, partial tile, deleted image), and a lane keeps,
+// in place of the one query's popcount, the 2^NP subset counts
+//   S_T = popcount(live & AND_{k in T} x_k),  T a set of planes (S_0: the live rows),
+// one AND and one popcount-accumulate each; m_i follows from them by inclusion-
+// exclusion, once per block.  k_scan_bits1 drops a tile the clamp loads again
+// as a whole and masks the partial tile's result; here S_0 and the all-zero
+// minterm count rows on their own, so (1) such a tile adds to no counter and
+// (2) in the partial tile `valid` is the live rows of every subset.  After
+// the block's exact reduction thread m < members works count_m out of the
+// block's totals and hands it in as member m's own launch would: its ticket
+// area (that of its position in the chain), count word or frame, nan_out.
+struct Bits1Group {
+  int64_t nrows;
+  int32_t tiles_per_block;
+  uint16_t first, count;               // its members: m[first, first + count)
+  const uint32_t* pl[kSliceMaxTerms];
+  const uint64_t* deleted;             // device or null
+};
+struct Bits1Member {
+  int64_t* out;      // the count word (kPlaneFinPacked) / the count frame (kPlaneFinFrame)
+  uint32_t* ticket;  // kPlaneFinPacked
+  int32_t* nan_out;
+  uint32_t table;
+  int32_t ticket_groups;
+};
+struct Bits1Shared {
+  Bits1Group g[kMaxFuse];   // what the first plane load needs
+  Bits1Member m[kMaxFuse];  // in group order
+  uint32_t nb;              // blocks per group
+  uint32_t pad_;
+};
+static_assert(sizeof(Bits1Group) == 56 && sizeof(Bits1Member) == 32, "k_scan_bits1_shared's records");
+static_assert(sizeof(Bits1Shared) == kMaxFuse * 88 + 8 && sizeof(Bits1Shared) <= 4096, "the groups fit the kernel arguments");
+
+constexpr int bits1_top_plane(int s) { return s >= 8 ? 3 : (s >= 4 ? 2 : (s >= 2 ? 1 : 0)); }
+
+// c[T] += S_T of one dword: a[T] = a[T without its top plane] & that plane
+template <int NP, bool LIVE>
+__device__ __forceinline__ void bits1_subsets(uint32_t (&c)[1 << NP], const uint32_t (&x)[NP], uint32_t live) {
+  uint32_t a[1 << NP];
+  a[0] = live;
+  if (LIVE) c[0] += (uint32_t)__popc(live);
+#pragma unroll
+  for (int s = 1; s < (1 << NP); ++s) {
+    const int k = bits1_top_plane(s), rest = s ^ (1 << k);
+    a[s] = (rest == 0 && !LIVE) ? x[k] : (a[rest] & x[k]);
+    c[s] += (uint32_t)__popc(a[s]);
+  }
+}
+
+// 8 waves per SIMD like k_scan_bits1; four planes' 16 counters are not held to it (they spill if they are)
+template <int NP, bool DEL, int FIN>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NP >= 4 ? 4 : 8, 8))) void k_scan_bits1_shared(
+    Bits1Shared S) {
+  static_assert(NP >= 1 && NP <= kSliceMaxTerms, "a chain without planes stays one grid row per query");
+  if (blockIdx.x >= S.nb) return;
+  const Bits1Group& P = S.g[blockIdx.y];
+  constexpr int kB = bits1_batch(NP, DEL);
+  constexpr int kM = 1 << NP;
+  constexpr int kTileDwords = kBitTileRows / 32;
+  const uint32_t nblocks = S.nb;
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)uniform(threadIdx.x >> 6);
+  const int members = P.count;
+  // Thread m's member record is a vector load from the kernel arguments (threads past the group's
+  // members read its last one and drop it), issued after the last tile.  Left alone, hipcc sinks it
+  // below the barrier, a whole round trip on the block's tail; member_pin holds it above the barrier
+  // and waits for it there, so the block's reduction covers most of the trip.  (Issued before the
+  // first plane load it costs that load a wait: hipcc settles every pending load at the loop's head.)
+  const Bits1Member& Mr = S.m[P.first + min((int)threadIdx.x, members - 1)];
+  uint64_t out = 0, ticket = 0, nan_out = 0;
+  uint32_t table = 0;
+  int32_t groups = 0;
+  auto member_load = [&]() {
+    out = reinterpret_cast<uint64_t>(Mr.out);
+    table = Mr.table;
+    if constexpr (FIN == kPlaneFinPacked) {
+      ticket = reinterpret_cast<uint64_t>(Mr.ticket);
+      nan_out = reinterpret_cast<uint64_t>(Mr.nan_out);
+      groups = Mr.ticket_groups;
+    }
+  };
+  auto member_pin = [&]() {
+    if constexpr (FIN == kPlaneFinPacked)
+      asm volatile("" : "+v"(out), "+v"(ticket), "+v"(nan_out), "+v"(table), "+v"(groups));
+    else
+      asm volatile("" : "+v"(out), "+v"(table));
+  };
+  const int tp = (int)(P.nrows / kBitTileRows);     // the full tiles = the partial tile's number
+  const int prows = (int)(P.nrows % kBitTileRows);  // the partial tile's rows
+  const int t0 = (int)blockIdx.x * P.tiles_per_block;
+  const int t1 = min(t0 + P.tiles_per_block, tp + (prows != 0 ? 1 : 0));
+  const uint32_t* pl[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) pl[k] = P.pl[k];
+  gu32* del = (gu32*)P.deleted;
+  const bool del16 = DEL && (reinterpret_cast<uintptr_t>(P.deleted) & 15) == 0;  // uniform
+
+  uint32_t c[kM];  // the lane's S_T
+#pragma unroll
+  for (int s = 0; s < kM; ++s) c[s] = 0u;
+  const int tf = min(t1, tp);  // full tiles in the main loop
+  for (int base = min(t0 + wave, tf); base < tf; base += kWaves * kB) {
+    v4u x[kB][NP], dead[kB];
+    // every load of the batch, unconditional; a tile past the full tiles is the last one again, and is not counted
+    int64_t dw[kB];  // the tile's first dword in every plane (uniform)
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+      dw[u] = (int64_t)min(base + u * kWaves, tf - 1) * kTileDwords;
+#pragma unroll
+      for (int k = 0; k < NP; ++k) x[u][k] = bit_tile_load(pl[k] + dw[u], lane);
+    }
+    if (DEL) {
+      if (del16) {
+#pragma unroll
+        for (int u = 0; u < kB; ++u) dead[u] = bit_tile_load(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
+      } else {
+#pragma unroll
+        for (int u = 0; u < kB; ++u) {
+          gu32* d = (gu32*)bit_tile_lane(reinterpret_cast<const uint32_t*>(P.deleted) + dw[u], lane);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dead[u][i] = d[i];
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // no use of a loaded tile is scheduled among the loads: one wait, after the last
+
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+      if (base + u * kWaves < tf) {  // uniform: a tile loaded again counts nowhere, S_0 included
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t xi[NP];
+#pragma unroll
+          for (int k = 0; k < NP; ++k) xi[k] = x[u][k][i];
+          bits1_subsets<NP, DEL>(c, xi, DEL ? ~dead[u][i] : ~0u);
+        }
+        if (!DEL) c[0] += 128u;  // the lane's rows of a full tile, all live
+      }
+    }
+  }
+  // the partial tile, owned like any other tile of [t0, t1)
+  if (prows != 0 && tp >= t0 + wave && tp < t1 && (tp - t0 - wave) % kWaves == 0) {
+    v4u xp[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) xp[k] = bit_tile_load(pl[k] + (int64_t)tp * kTileDwords, lane);
+    const int64_t dw = (int64_t)tp * kTileDwords + lane * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rem = prows - (lane * 4 + i) * 32;  // the dword's rows below nrows
+      uint32_t valid = rem >= 32 ? ~0u : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+      if (DEL && rem > 0) valid &= ~del[dw + i];
+      uint32_t xi[NP];
+#pragma unroll
+      for (int k = 0; k < NP; ++k) xi[k] = xp[k][i];
+      bits1_subsets<NP, true>(c, xi, valid);
+    }
+  }
+  member_load();
+  // The block's S_T, exact.  A lane's counter is at most 128 rows x its wave's tiles of the segment,
+  // below wave_sum_dpp's 2^26 for any segment under 2^20 tiles: one sum per counter; else wave_count's two.
+  __shared__ uint64_t wsum[kWaves][kM];
+  const bool small = P.tiles_per_block < (1 << 20);  // uniform
+#pragma unroll
+  for (int s = 0; s < kM; ++s) {
+    const uint64_t wc = small ? (uint64_t)wave_sum_dpp(c[s]) : wave_count(c[s]);
+    if (lane == 0) wsum[wave][s] = wc;
+  }
+  member_pin();
+  __syncthreads();
+  if ((int)threadIdx.x >= members) return;
+  // member threadIdx.x, from here on in lanes of their own: nothing below is forced uniform
+  uint64_t f[kM];
+#pragma unroll
+  for (int s = 0; s < kM; ++s) {
+    f[s] = wsum[0][s];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) f[s] += wsum[w][s];
+  }
+#pragma unroll
+  for (int k = 0; k < NP; ++k)  // S_T -> m_i: rows that hold T's planes and none of the others
+#pragma unroll
+    for (int s = 0; s < kM; ++s)
+      if (((s >> k) & 1) == 0) f[s] -= f[s | (1 << k)];
+  uint64_t total = 0;
+#pragma unroll
+  for (int s = 0; s < kM; ++s) total += ((table >> s) & 1u) != 0u ? f[s] : 0ull;
+  if (FIN == kPlaneFinFrame)  // result unused: a no-return atomic, nothing waits for it in the block
+    __hip_atomic_fetch_add(reinterpret_cast<uint64_t*>(out) + (blockIdx.x % kFrameSlots) * kFrameSlotStride,
+                           pack_count((int64_t)total, 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    packed_count_finalize(reinterpret_cast<uint32_t*>(ticket), groups, (int64_t)total, 0,
+                          reinterpret_cast<int64_t*>(out), reinterpret_cast<int32_t*>(nan_out), nblocks);
+}
+
 // planes 0..w-1 of 64 rows per wave step: one ballot per plane, lane j stores
 // plane j's 64 bits (rows past nrows, up to the padded plane length, as 0)
 __global__ __launch_bounds__(kBlock) void k_bitslice_build(const int32_t* __restrict__ col, int64_t nrows,
@@ -832,7 +1033,10 @@ struct Bits1Fuse {
   unsigned gx = 0;      // its blocks per query
   int n = 0;            // its queries
   int64_t launches = 0, scans = 0;  // this capture: nodes that hold more than one query, the queries in them
+  int64_t groups = 0, shared = 0;   // this capture: the plane groups of those nodes, the queries in groups of several
+  int chain_groups = 0, chain_shared = 0;  // the chain's part of both (0 while it is one query)
   Bits1Batch B;
+  Bits1Shared S;  // B by plane groups, when one of them holds two queries
 };
 
 Bits1Fuse* bits1_fuse_new() { return new (std::nothrow) Bits1Fuse(); }
@@ -842,14 +1046,19 @@ void bits1_fuse_begin(Bits1Fuse* f, bool on) {
   f->node = nullptr;
   f->n = 0;
   f->launches = f->scans = 0;
+  f->groups = f->shared = 0;
+  f->chain_groups = f->chain_shared = 0;
 }
 void bits1_fuse_cut(Bits1Fuse* f) {
   f->node = nullptr;
   f->n = 0;
 }
-void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans) {
+void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans, int64_t* plane_groups,
+                    int64_t* shared_scans) {
   if (fused_launches) *fused_launches = f->launches;
   if (fused_scans) *fused_scans = f->scans;
+  if (plane_groups) *plane_groups = f->groups;
+  if (shared_scans) *shared_scans = f->shared;
   f->on = false;
   f->node = nullptr;
   f->n = 0;
@@ -886,7 +1095,51 @@ static void bits1_fuse_start(Bits1Fuse* f, const Bits1Launch& P, int key, dim3 g
   f->key = key;
   f->gx = grid.x;
   f->n = 1;
+  f->chain_groups = f->chain_shared = 0;
   f->B.q[0] = P;
+}
+
+// The chain's n queries by plane groups, in f->S: query j joins the first group whose planes (slot
+// for slot), deleted image, rows and segment are its own, else opens one; members in group order,
+// each with the ticket area of its place in the chain.  Returns the groups; *shared: the queries
+// in groups of several.
+static int bits1_fuse_groups(Bits1Fuse* f, int n, int* shared) {
+  int of[kMaxFuse], ng = 0;
+  Bits1Shared& S = f->S;
+  for (int j = 0; j < n; ++j) {
+    const Bits1Launch& q = f->B.q[j];
+    int g = 0;
+    for (; g < ng; ++g) {
+      const Bits1Group& G = S.g[g];
+      bool same = G.nrows == q.nrows && G.tiles_per_block == q.tiles_per_block && G.deleted == q.deleted;
+      for (int k = 0; k < kSliceMaxTerms; ++k) same = same && G.pl[k] == q.pl[k];
+      if (same) break;
+    }
+    if (g == ng) {
+      Bits1Group& G = S.g[ng++];
+      G.nrows = q.nrows;
+      G.tiles_per_block = q.tiles_per_block;
+      G.count = 0;
+      for (int k = 0; k < kSliceMaxTerms; ++k) G.pl[k] = q.pl[k];
+      G.deleted = q.deleted;
+    }
+    S.g[g].count += 1;
+    of[j] = g;
+  }
+  int at = 0;
+  *shared = 0;
+  for (int g = 0; g < ng; ++g) {
+    S.g[g].first = (uint16_t)at;
+    if (S.g[g].count > 1) *shared += S.g[g].count;
+    for (int j = 0; j < n; ++j)
+      if (of[j] == g) {
+        const Bits1Launch& q = f->B.q[j];
+        S.m[at++] = Bits1Member{q.out, q.ticket, q.nan_out, q.table, q.ticket_groups};
+      }
+  }
+  S.nb = f->gx;
+  S.pad_ = 0;
+  return ng;
 }
 
 // true: P is grid row f->n of the chain's node now and needs no launch
@@ -904,11 +1157,21 @@ static bool bits1_fuse_join(Bits1Fuse* f, Bits1Launch P, dim3 grid, hipStream_t 
   if (!tail || tail != f->node) return false;  // something else was recorded since (or the call failed)
   if (FIN == kPlaneFinPacked) P.ticket += (size_t)f->n * kTicketWords;
   f->B.q[f->n] = P;
+  int shared = 0;
+  int groups = bits1_fuse_groups(f, f->n + 1, &shared);
+  if (NP == 0) groups = f->n + 1, shared = 0;  // no planes to share: every query a group of its own
   void* args[1] = {&f->B};
   hipKernelNodeParams kp{};
   kp.func = reinterpret_cast<void*>(&k_scan_bits1_batch<NP, DEL, FIN>);
   f->B.nb = f->gx;
   kp.gridDim = dim3((f->gx + kXcds - 1) / kXcds * kXcds, (unsigned)(f->n + 1));
+  if constexpr (NP > 0) {
+    if (shared > 0) {  // a group of several: one grid row per group, groups of one ride along
+      args[0] = &f->S;
+      kp.func = reinterpret_cast<void*>(&k_scan_bits1_shared<NP, DEL, FIN>);
+      kp.gridDim.y = (unsigned)groups;
+    }
+  }
   kp.blockDim = dim3(kBlock);
   kp.sharedMemBytes = 0;
   kp.kernelParams = args;
@@ -920,6 +1183,10 @@ static bool bits1_fuse_join(Bits1Fuse* f, Bits1Launch P, dim3 grid, hipStream_t 
   f->n += 1;
   f->launches += f->n == 2 ? 1 : 0;
   f->scans += f->n == 2 ? 2 : 1;
+  f->groups += groups - f->chain_groups;
+  f->shared += shared - f->chain_shared;
+  f->chain_groups = groups;
+  f->chain_shared = shared;
   return true;
 }
 

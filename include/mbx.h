@@ -544,7 +544,20 @@ int mbx_comm_allgather_count_all(mbx_comm *const *comms, int32_t n, const int64_
  * columns term for term, the same deleted image) form a plane group: the launch
  * reads a group's planes once and every member's count comes out of that pass.
  * mbx_graph_plane_groups: the plane groups over the graph's launches that hold
- * more than one scan, and the scans in groups of more than one. */
+ * more than one scan, and the scans in groups of more than one.
+ * Replay form.  A graph that is exactly one kernel node, and that node a run of
+ * such COUNT scans (one scan included; graph_fuse_counts on), is *eligible*:
+ * mbx_graph_launch then issues that kernel itself -- same kernel, grid,
+ * arguments and stream as the node -- instead of handing the graph to the
+ * runtime (form 1, "direct": the default of an eligible graph; about a quarter
+ * of the host time per replay).  Every other graph -- a second kernel, a memset,
+ * a collective, an exchange-stream join, two runs in a line -- is replayed by
+ * the runtime (form 0).  One node is the rule because that is the case that was
+ * measured.  Launched while its context has a capture open, a graph in the
+ * direct form is recorded as a kernel node of the graph being captured.
+ * mbx_graph_set_replay: form 0 or 1; 1 on a graph that is not eligible is
+ * MBX_E_INVALID and changes nothing.  mbx_graph_replay_form: the form in use
+ * and whether the graph is eligible (either pointer may be null). */
 typedef struct mbx_graph mbx_graph;
 int mbx_graph_begin(mbx_ctx *ctx);
 int mbx_graph_end(mbx_ctx *ctx, mbx_graph **out);
@@ -552,6 +565,8 @@ int mbx_graph_launch(mbx_graph *g);
 int mbx_graph_free(mbx_graph *g);
 int mbx_graph_info(const mbx_graph *g, int64_t *nodes, int64_t *fused_launches, int64_t *fused_scans);
 int mbx_graph_plane_groups(const mbx_graph *g, int64_t *groups, int64_t *shared_scans);
+int mbx_graph_set_replay(mbx_graph *g, int32_t form);
+int mbx_graph_replay_form(const mbx_graph *g, int32_t *form, int32_t *eligible);
 
 /* ---- device result slots for callers without a HIP allocator of their own
  * (the JNI glue: *_async results and the collectives' buffers live in device

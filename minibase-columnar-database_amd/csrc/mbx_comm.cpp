@@ -40,6 +40,8 @@ struct mbx_graph {
   int64_t nodes = 0;                            // mbx_graph_info
   int64_t fused_launches = 0, fused_scans = 0;  // the capture's COUNT chains (Bits1Fuse, mbx_planes.hip)
   int64_t plane_groups = 0, shared_scans = 0;   // mbx_graph_plane_groups
+  Bits1Replay* replay = nullptr;                // the graph is one COUNT-chain kernel node: that launch, else null
+  int32_t form = 0;                             // mbx_graph_set_replay: 0 hipGraphLaunch, 1 the record's launch
 };
 
 #define NCCLCHK(expr)                                                                             \
@@ -418,7 +420,9 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   HIPCHK(hipSetDevice(c->device));
   c->capturing = false;
   int64_t fused_launches = 0, fused_scans = 0, plane_groups = 0, shared_scans = 0;
-  bits1_fuse_end(c->fuse, &fused_launches, &fused_scans, &plane_groups, &shared_scans);  // whatever becomes of the capture, its chain is over
+  Bits1Replay* replay = nullptr;
+  // whatever becomes of the capture, its chain is over
+  bits1_fuse_end(c->fuse, &fused_launches, &fused_scans, &plane_groups, &shared_scans, c->stream, &replay);
   // the exchange stream's captured work joins the origin stream (a capture
   // ends only with every forked stream joined back); the capture is ended
   // even when the join (or anything captured before it) failed, so the
@@ -432,11 +436,13 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
   const hipError_t ee = hipStreamEndCapture(c->stream, &g);
   if (je != hipSuccess || ee != hipSuccess) {
     if (g) hipGraphDestroy(g);
+    bits1_replay_free(replay);
     return fail(MBX_E_DEVICE, "graph_end: %s", hipGetErrorString(je != hipSuccess ? je : ee));
   }
   mbx_graph* mg = new (std::nothrow) mbx_graph();
   if (!mg) {
     hipGraphDestroy(g);
+    bits1_replay_free(replay);
     return fail(MBX_E_NOMEM, "graph: host allocation");
   }
   mg->ctx = c;
@@ -450,9 +456,19 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
     mg->nodes = (int64_t)nn;
   else
     (void)hipGetLastError();
+  // A replay of a graph that is one chain node is that kernel on the context stream and nothing
+  // else, so mbx_graph_launch may issue it itself.  Anything recorded beside the chain -- a second
+  // kernel, a memset, a collective, the exchange stream's join -- is a node: no record then.
+  if (replay && mg->nodes == 1) {
+    mg->replay = replay;
+    mg->form = 1;
+  } else {
+    bits1_replay_free(replay);
+  }
   const hipError_t e = hipGraphInstantiate(&mg->exec, g, nullptr, nullptr, 0);
   if (e != hipSuccess) {
     hipGraphDestroy(g);
+    bits1_replay_free(mg->replay);
     delete mg;
     return fail(MBX_E_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(e));
   }
@@ -463,7 +479,30 @@ extern "C" int mbx_graph_end(mbx_ctx* c, mbx_graph** out) {
 extern "C" int mbx_graph_launch(mbx_graph* g) {
   NOTNULL(g);
   HIPCHK(hipSetDevice(g->ctx->device));
+  if (g->replay && g->form == 1) {
+    // While the context records another graph the launch is recorded too, a kernel node of that
+    // graph and the end of any chain before it.  (The runtime's form is not: hipGraphLaunch on a
+    // capturing stream runs the graph at once here and leaves the outer graph without it.)
+    if (g->ctx->capturing) bits1_fuse_cut(g->ctx->fuse);
+    HIPCHK(bits1_replay_launch(g->replay, g->ctx->stream));
+    return MBX_OK;
+  }
   HIPCHK(hipGraphLaunch(g->exec, g->ctx->stream));
+  return MBX_OK;
+}
+
+extern "C" int mbx_graph_set_replay(mbx_graph* g, int32_t form) {
+  NOTNULL(g);
+  if (form != 0 && form != 1) return fail(MBX_E_INVALID, "graph_set_replay: form %d", (int)form);
+  if (form == 1 && !g->replay) return fail(MBX_E_INVALID, "graph_set_replay: the graph is not one COUNT-chain kernel");
+  g->form = form;
+  return MBX_OK;
+}
+
+extern "C" int mbx_graph_replay_form(const mbx_graph* g, int32_t* form, int32_t* eligible) {
+  NOTNULL(g);
+  if (form) *form = g->form;
+  if (eligible) *eligible = g->replay ? 1 : 0;
   return MBX_OK;
 }
 
@@ -488,6 +527,7 @@ extern "C" int mbx_graph_free(mbx_graph* g) {
   hipStreamSynchronize(g->ctx->stream);
   if (g->exec) hipGraphExecDestroy(g->exec);
   if (g->graph) hipGraphDestroy(g->graph);
+  bits1_replay_free(g->replay);
   delete g;
   return MBX_OK;
 }

@@ -592,8 +592,14 @@ Bits1Fuse* bits1_fuse_new();
 void bits1_fuse_free(Bits1Fuse* f);
 void bits1_fuse_begin(Bits1Fuse* f, bool on);
 void bits1_fuse_cut(Bits1Fuse* f);  // the chain ends here: the next launch starts a new one (a collective)
+// *replay (when asked for): a record of the chain's node -- kernel, grid, its arguments by value --
+// if a chain is live and its node is still the tail of the capture on s, else null; the caller owns
+// it.  bits1_replay_launch issues that launch on s: what the node does in a replay of the graph.
+struct Bits1Replay;
 void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans, int64_t* plane_groups,
-                    int64_t* shared_scans);
+                    int64_t* shared_scans, hipStream_t s = nullptr, Bits1Replay** replay = nullptr);
+hipError_t bits1_replay_launch(const Bits1Replay* r, hipStream_t s);
+void bits1_replay_free(Bits1Replay* r);
 // bit-plane BitSet scan (k_scan_bits_words): L.bp set; the grid is the output bitmap's, so
 // L.tiles_per_block keeps its 256-row meaning (a segment of tiles_per_block x 4 words); writes
 // every word of L.out_words and L.seg_counts[block].  L.words_wt is not honoured: plain stores

@@ -1031,12 +1031,28 @@ struct Bits1Fuse {
   hipGraphNode_t node = nullptr;  // the chain's kernel node, the capture's tail when it was recorded; null: no chain
   int key = 0;          // bits1_key of the chain's instantiation
   unsigned gx = 0;      // its blocks per query
+  void* func = nullptr; // the node's kernel and grid as last set: what a replay record repeats
+  dim3 grid;
   int n = 0;            // its queries
   int64_t launches = 0, scans = 0;  // this capture: nodes that hold more than one query, the queries in them
   int64_t groups = 0, shared = 0;   // this capture: the plane groups of those nodes, the queries in groups of several
   int chain_groups = 0, chain_shared = 0;  // the chain's part of both (0 while it is one query)
   Bits1Batch B;
   Bits1Shared S;  // B by plane groups, when one of them holds two queries
+};
+
+// What the chain's node runs, by value: mbx_graph_launch repeats it as a plain launch when the node
+// is the whole graph.  The arguments are the node's own -- k_scan_bits1's record for a chain of one,
+// the batch, or the plane groups.
+struct Bits1Replay {
+  void* func;
+  dim3 grid;
+  union Args {
+    Bits1Launch one;
+    Bits1Batch batch;
+    Bits1Shared shared;
+    Args() {}
+  } a;
 };
 
 Bits1Fuse* bits1_fuse_new() { return new (std::nothrow) Bits1Fuse(); }
@@ -1053,8 +1069,28 @@ void bits1_fuse_cut(Bits1Fuse* f) {
   f->node = nullptr;
   f->n = 0;
 }
+static hipGraphNode_t bits1_capture_tail(Bits1Fuse* f, hipStream_t s);
+
 void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans, int64_t* plane_groups,
-                    int64_t* shared_scans) {
+                    int64_t* shared_scans, hipStream_t s, Bits1Replay** replay) {
+  if (replay) {
+    *replay = nullptr;
+    // a live chain whose node is still the last thing recorded; whether it is the only thing is the caller's to see
+    if (f->on && f->node && f->n >= 1 && f->func && bits1_capture_tail(f, s) == f->node) {
+      Bits1Replay* r = new (std::nothrow) Bits1Replay();
+      if (r) {
+        r->func = f->func;
+        r->grid = f->grid;
+        if (f->n == 1)
+          r->a.one = f->B.q[0];
+        else if (f->chain_shared > 0)
+          r->a.shared = f->S;
+        else
+          r->a.batch = f->B;
+        *replay = r;
+      }
+    }
+  }
   if (fused_launches) *fused_launches = f->launches;
   if (fused_scans) *fused_scans = f->scans;
   if (plane_groups) *plane_groups = f->groups;
@@ -1062,6 +1098,12 @@ void bits1_fuse_end(Bits1Fuse* f, int64_t* fused_launches, int64_t* fused_scans,
   f->on = false;
   f->node = nullptr;
   f->n = 0;
+}
+
+void bits1_replay_free(Bits1Replay* r) { delete r; }
+hipError_t bits1_replay_launch(const Bits1Replay* r, hipStream_t s) {
+  void* args[1] = {const_cast<Bits1Replay::Args*>(&r->a)};
+  return hipLaunchKernel(r->func, r->grid, dim3(kBlock), args, 0, s);
 }
 
 constexpr int bits1_key(int np, bool del, int fin) { return np * 4 + (del ? 2 : 0) + (fin == kPlaneFinFrame ? 1 : 0); }
@@ -1086,7 +1128,7 @@ static hipGraphNode_t bits1_capture_tail(Bits1Fuse* f, hipStream_t s) {
 }
 
 // the launch just recorded starts a chain of one: today's single kernel node
-static void bits1_fuse_start(Bits1Fuse* f, const Bits1Launch& P, int key, dim3 grid, hipStream_t s) {
+static void bits1_fuse_start(Bits1Fuse* f, const Bits1Launch& P, int key, void* func, dim3 grid, hipStream_t s) {
   f->node = nullptr;
   hipGraphNode_t tail = bits1_capture_tail(f, s);
   hipGraphNodeType ty = hipGraphNodeTypeEmpty;
@@ -1094,6 +1136,8 @@ static void bits1_fuse_start(Bits1Fuse* f, const Bits1Launch& P, int key, dim3 g
   f->node = tail;
   f->key = key;
   f->gx = grid.x;
+  f->func = func;
+  f->grid = grid;
   f->n = 1;
   f->chain_groups = f->chain_shared = 0;
   f->B.q[0] = P;
@@ -1181,6 +1225,8 @@ static bool bits1_fuse_join(Bits1Fuse* f, Bits1Launch P, dim3 grid, hipStream_t 
     return false;
   }
   f->n += 1;
+  f->func = kp.func;
+  f->grid = kp.gridDim;
   f->launches += f->n == 2 ? 1 : 0;
   f->scans += f->n == 2 ? 2 : 1;
   f->groups += groups - f->chain_groups;
@@ -1194,7 +1240,8 @@ template <int NP, bool DEL, int FIN>
 static void bits1_launch_del(const Bits1Launch& P, dim3 grid, hipStream_t s, Bits1Fuse* fuse) {
   if (fuse && bits1_fuse_join<NP, DEL, FIN>(fuse, P, grid, s)) return;
   hipLaunchKernelGGL((k_scan_bits1<NP, DEL, FIN>), grid, dim3(kBlock), 0, s, P);
-  if (fuse && fuse->on) bits1_fuse_start(fuse, P, bits1_key(NP, DEL, FIN), grid, s);
+  if (fuse && fuse->on)
+    bits1_fuse_start(fuse, P, bits1_key(NP, DEL, FIN), reinterpret_cast<void*>(&k_scan_bits1<NP, DEL, FIN>), grid, s);
 }
 
 template <int NP, int FIN>

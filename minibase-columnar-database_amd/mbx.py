@@ -106,7 +106,7 @@ EXPORTS = [
     "mbx_comm_allgather_count_async", "mbx_comm_allreduce_count_all", "mbx_comm_allreduce_agg_all",
     "mbx_comm_allgather_count_all",
     "mbx_graph_begin", "mbx_graph_end", "mbx_graph_launch", "mbx_graph_free", "mbx_graph_info",
-    "mbx_graph_plane_groups",
+    "mbx_graph_plane_groups", "mbx_graph_set_replay", "mbx_graph_replay_form",
     # include/mbx_db.h
     "mbx_db_create", "mbx_db_open", "mbx_db_close", "mbx_db_info", "mbx_db_file_entry", "mbx_db_columnar_create",
     "mbx_db_columnar_insert", "mbx_db_columnar_info", "mbx_db_mark_deleted", "mbx_db_bitmap_write",
@@ -270,6 +270,8 @@ def lib():
         "mbx_graph_free": ([V], ctypes.c_int),
         "mbx_graph_info": ([V, P(I64), P(I64), P(I64)], ctypes.c_int),
         "mbx_graph_plane_groups": ([V, P(I64), P(I64)], ctypes.c_int),
+        "mbx_graph_set_replay": ([V, I32], ctypes.c_int),
+        "mbx_graph_replay_form": ([V, P(I32), P(I32)], ctypes.c_int),
         "mbx_db_create": ([ctypes.c_char_p, I32, P(V)], ctypes.c_int),
         "mbx_db_open": ([ctypes.c_char_p, P(V)], ctypes.c_int),
         "mbx_db_close": ([V], ctypes.c_int),
@@ -970,13 +972,22 @@ class Graph:
         """mbx_graph_info: {"nodes", "fused_launches", "fused_scans"} -- the graph's nodes, and how many
         of them hold a run of COUNT scans (graph_fuse_counts) with how many scans in all; and
         mbx_graph_plane_groups: {"plane_groups", "shared_scans"} -- the plane groups of those runs (scans
-        that read the same planes, read once per group) and the scans in groups of more than one."""
+        that read the same planes, read once per group) and the scans in groups of more than one; and
+        mbx_graph_replay_form: {"replay", "replay_eligible"} -- "direct" (launch() issues the graph's one
+        kernel itself) or "graph", and whether the graph may take the direct form at all."""
         n, fl, fs = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         pg, ss = ctypes.c_int64(0), ctypes.c_int64(0)
+        form, el = ctypes.c_int32(0), ctypes.c_int32(0)
+        _chk(lib().mbx_graph_replay_form(self.h, ctypes.byref(form), ctypes.byref(el)))
         _chk(lib().mbx_graph_info(self.h, ctypes.byref(n), ctypes.byref(fl), ctypes.byref(fs)))
         _chk(lib().mbx_graph_plane_groups(self.h, ctypes.byref(pg), ctypes.byref(ss)))
         return {"nodes": n.value, "fused_launches": fl.value, "fused_scans": fs.value,
-                "plane_groups": pg.value, "shared_scans": ss.value}
+                "plane_groups": pg.value, "shared_scans": ss.value,
+                "replay": "direct" if form.value == 1 else "graph", "replay_eligible": bool(el.value)}
+
+    def set_replay(self, form):
+        """mbx_graph_set_replay: "direct" / 1 or "graph" / 0; direct on a graph that is not eligible raises."""
+        _chk(lib().mbx_graph_set_replay(self.h, {"graph": 0, "direct": 1}.get(form, form)))
 
     def close(self):
         if getattr(self, "h", None):

@@ -23,10 +23,21 @@ is checked against a torch reduction of the same columns.  Prints one JSON
 line: per case and knob value the median and the extremes of us per scan, the
 graph's nodes, and `gain_us` = median(0) - median(1).
 
-    python tools/bench_fused_counts.py [--rows N] [--graph-steps K] [--rounds R] [--launches L]
-                                       [--case distinct|same|tables|single|both|all] [--fuse 0|1|both]
+A graph that is one fused-chain kernel may be replayed by the library as a plain
+launch (Graph.set_replay).  --replay graph (the default) measures every graph
+through the runtime's graph launch, as before that form existed; --replay direct
+measures eligible graphs in the direct form; --replay both measures an eligible
+graph in both forms alternately in the same rounds: the runtime's under its knob
+value ("1"), the direct one under "1:direct", with `direct_gain_us` =
+median("1") - median("1:direct").  A graph that is not eligible (knob 0 with
+more than one scan) has the runtime's form only.
 
---case both: distinct and same (the default); all: the four cases.
+    python tools/bench_fused_counts.py [--rows N] [--graph-steps K | --scans K] [--rounds R] [--launches L]
+                                       [--case distinct|same|tables|single|both|all] [--fuse 0|1|both]
+                                       [--replay graph|direct|both]
+
+--case both: distinct and same (the default); all: the four cases.  --scans is
+--graph-steps by its other name: the scans of one chain.
 
 --case / --fuse narrow the run to one graph (a profiler's run: rocprofv3
 counters see one kernel form).
@@ -45,11 +56,12 @@ THRESH = 1 << 19
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
-    ap.add_argument("--graph-steps", type=int, default=20)
+    ap.add_argument("--graph-steps", "--scans", dest="graph_steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--case", choices=["distinct", "same", "tables", "single", "both", "all"], default="both")
     ap.add_argument("--fuse", choices=["0", "1", "both"], default="both")
+    ap.add_argument("--replay", choices=["graph", "direct", "both"], default="graph")
     args = ap.parse_args()
 
     import torch
@@ -120,31 +132,45 @@ def main():
                 graphs[knob] = ctx.graph_end()
             ctx.set_tuning("graph_fuse_counts", 1)
         want = [w for _, w in steps[case]] + [0] * (len(out) - K)
-        times = {knob: [] for knob in knobs}
-        for g in graphs.values():  # first replay: untimed, checked
+        # what is measured: (key, graph, replay form); an eligible graph may have two entries
+        runs = []
+        for knob in knobs:
+            eligible = graphs[knob].info()["replay_eligible"]
+            if args.replay != "direct" or not eligible:
+                runs.append((str(knob), graphs[knob], "graph"))
+            if args.replay != "graph" and eligible:
+                runs.append((str(knob) if args.replay == "direct" else f"{knob}:direct", graphs[knob], "direct"))
+        times = {key: [] for key, _, _ in runs}
+        for _, g, form in runs:  # first replay: untimed, checked
             out.zero_()
             torch.cuda.synchronize()
+            g.set_replay(form)
             g.launch()
             ctx.sync()
             assert out.cpu().tolist() == want, (case, out.cpu().tolist(), want)
         for _ in range(args.rounds):
-            for knob in knobs:
+            for key, g, form in runs:
+                g.set_replay(form)
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record(ext)
                 for _ in range(args.launches):
-                    graphs[knob].launch()
+                    g.launch()
                 b.record(ext)
                 ctx.sync()
-                times[knob].append(a.elapsed_time(b) * 1e3 / (args.launches * K))
-                assert out.cpu().tolist() == want, (case, knob)
+                times[key].append(a.elapsed_time(b) * 1e3 / (args.launches * K))
+                assert out.cpu().tolist() == want, (case, key)
         rec = {}
-        for knob in knobs:
-            t = times[knob]
-            rec[str(knob)] = {"us_per_scan_median": statistics.median(t), "us_per_scan_min": min(t),
-                              "us_per_scan_max": max(t), **graphs[knob].info()}
-            graphs[knob].close()
+        for key, g, form in runs:
+            t = times[key]
+            g.set_replay(form)
+            rec[key] = {"us_per_scan_median": statistics.median(t), "us_per_scan_min": min(t),
+                        "us_per_scan_max": max(t), **g.info()}
+        for g in graphs.values():
+            g.close()
         if len(knobs) == 2:
             rec["gain_us"] = rec["0"]["us_per_scan_median"] - rec["1"]["us_per_scan_median"]
+        if "1" in rec and "1:direct" in rec:
+            rec["direct_gain_us"] = rec["1"]["us_per_scan_median"] - rec["1:direct"]["us_per_scan_median"]
         result["cases"][case] = rec
     for p in plans + [p for p, _ in extra]:
         p.close()

@@ -90,9 +90,10 @@ int mbx_db_columnar_insert(mbx_db* db, const char* name, int64_t nrows, const vo
 
 /* Columnarfile(name) (R/columnar/Columnarfile.java:194-300): schema from
  * cf.hdr.  cols / attr_names (16-byte cells, NUL terminated) may be null;
- * they hold max_cols entries.  *nrows = highest position + 1 (the table size
- * mbx_db_stage produces), *live = records in cf.0 minus deleted positions
- * (Columnarfile.getTupleCnt counts cf.dtid records instead). */
+ * they hold max_cols entries.  *nrows = highest position that holds a record
+ * + 1 (the table size mbx_db_stage produces; empty slots at the end of the
+ * last page are no rows), *live = records in cf.0 minus the cf.md positions
+ * below *nrows (Columnarfile.getTupleCnt counts cf.dtid records instead). */
 int mbx_db_columnar_info(mbx_db* db, const char* name, int32_t max_cols, int32_t* ncols, mbx_col_desc* cols,
                          char* attr_names, int64_t* nrows, int64_t* live);
 

@@ -228,6 +228,26 @@ int32_t hf_available(const uint8_t* pg) { return get16(pg + kFreeSpace) - kSlotS
 int32_t hf_slot_len(const uint8_t* pg, int32_t s) { return get16(pg + kDpFixed + s * kSlotSize); }
 int32_t hf_slot_off(const uint8_t* pg, int32_t s) { return (uint16_t)get16(pg + kDpFixed + s * kSlotSize + 2); }
 
+// The DataPageInfo record of directory slot s (not an empty slot), or null
+// when the slot is not an 8-byte record inside the page: a damaged slot must
+// not send the host up to 64 KiB past the page (or past the mapping).
+const uint8_t* dir_info(const uint8_t* dp, int32_t s) {
+  const int32_t off = hf_slot_off(dp, s);
+  if (hf_slot_len(dp, s) != kDpInfoSize || off + kDpInfoSize > kPage) return nullptr;
+  return dp + off;
+}
+
+// Slots of a data page up to the last one that holds a record.  Positions
+// exist only for records: the engine reaches them through firstRecord /
+// nextRecord, which skip EMPTY_SLOT (HFPage.java:467-531), and
+// findPosition(rid) (Heapfile.java:262-273); deleteRecord leaves slotCnt as
+// it was (HFPage.java:405-459), so empty slots at the end of the last page
+// are no rows.
+int32_t hf_used_slots(const uint8_t* pg, int32_t cnt) {
+  while (cnt > 0 && hf_slot_len(pg, cnt - 1) == -1) --cnt;
+  return cnt;
+}
+
 // HFPage.insertRecord: -1 when it does not fit
 int32_t hf_insert(uint8_t* pg, const uint8_t* rec, int32_t len) {
   int32_t free_space = get16(pg + kFreeSpace);
@@ -284,7 +304,8 @@ int heap_insert(mbx_db* db, int32_t first_dir, const uint8_t* rec, int32_t len, 
     const int32_t cnt = get16(dp + kSlotCnt);
     for (int32_t s = s0; s < cnt; ++s) {
       if (hf_slot_len(dp, s) == -1) continue;
-      const uint8_t* info = dp + hf_slot_off(dp, s);
+      const uint8_t* info = dir_info(dp, s);
+      if (!info) return fail(MBX_E_INVALID, "corrupt directory slot %d on page %d", s, dir);
       if (len <= get16(info)) {
         found_dir = dir;
         found_slot = s;
@@ -321,6 +342,8 @@ int heap_insert(mbx_db* db, int32_t first_dir, const uint8_t* rec, int32_t len, 
     s0 = 0;
   }
   uint8_t* dp = db->page(found_dir);
+  if (!dir_info(dp, found_slot))
+    return fail(MBX_E_INVALID, "corrupt directory slot %d on page %d", found_slot, found_dir);
   uint8_t* info = dp + hf_slot_off(dp, found_slot);
   const int32_t data_pid = get32(info + 4);
   uint8_t* pg = db->page(data_pid);
@@ -355,7 +378,8 @@ int heap_pages(mbx_db* db, int32_t first_dir, std::vector<DataPage>* out) {
     const int32_t cnt = get16(dp + kSlotCnt);
     for (int32_t s = 0; s < cnt && s < kRecsPerDirPage + 1; ++s) {
       if (hf_slot_len(dp, s) == -1) continue;
-      const uint8_t* info = dp + hf_slot_off(dp, s);
+      const uint8_t* info = dir_info(dp, s);
+      if (!info) return fail(MBX_E_INVALID, "corrupt directory slot %d on page %d", s, dir);
       DataPage d;
       d.index = dir_index * kRecsPerDirPage + s;
       d.pid = get32(info + 4);
@@ -769,7 +793,8 @@ int column_pages(mbx_db* db, const std::string& file, int32_t rec_len, ColumnPag
     if (cnt < 0 || cnt > cp->recs_per_page)
       return fail(MBX_E_INVALID, "%s: data page %d holds %d slots (max %d)", file.c_str(), d.pid, cnt,
                   cp->recs_per_page);
-    if (cnt > 0) cp->nrows = std::max(cp->nrows, d.index * cp->recs_per_page + cnt);
+    const int32_t used = hf_used_slots(db->page(d.pid), cnt);
+    if (used > 0) cp->nrows = std::max(cp->nrows, d.index * cp->recs_per_page + used);
     cp->records += d.recct;
   }
   return MBX_OK;
@@ -804,7 +829,11 @@ extern "C" int mbx_db_columnar_info(mbx_db* db, const char* name, int32_t max_co
       if (md != kInvalidPage) {
         std::vector<uint8_t> bytes;
         if ((rc = bm_read_bytes(db, md, &bytes))) return rc;
-        for (uint8_t b : bytes) del += __builtin_popcount(b);
+        // bits at or past nrows name no row (the staged table drops them too)
+        for (size_t k = 0; k < bytes.size() && (int64_t)k * 8 < cp.nrows; ++k) {
+          const int64_t left = cp.nrows - (int64_t)k * 8;
+          del += __builtin_popcount(left >= 8 ? bytes[k] : bytes[k] & ((1u << left) - 1u));
+        }
       }
       *live = cp.records - del;
     }
@@ -1019,9 +1048,10 @@ extern "C" int mbx_db_stage(mbx_ctx* c, mbx_db* db, const char* name, mbx_table*
 
 namespace {
 
-// the column's highest position + 1 from its directory and the slot counts
-// of its last non-empty data pages only (column_pages reads every data
-// page's header; a shard must not touch the other shards' pages)
+// the column's highest position + 1 from its directory and the slot
+// directories of its last data pages only, back to the first that holds a
+// record (column_pages reads every data page's header; a shard must not
+// touch the other shards' pages)
 int column_pages_lazy(mbx_db* db, const std::string& file, int32_t rec_len, ColumnPages* cp) {
   const int32_t first = get_file_entry(db, file);
   if (first == kInvalidPage) return fail(MBX_E_INVALID, "heapfile %s is missing", file.c_str());
@@ -1043,8 +1073,9 @@ int column_pages_lazy(mbx_db* db, const std::string& file, int32_t rec_len, Colu
     if (cnt < 0 || cnt > cp->recs_per_page)
       return fail(MBX_E_INVALID, "%s: data page %d holds %d slots (max %d)", file.c_str(), pid, cnt,
                   cp->recs_per_page);
-    if (cnt > 0) {
-      cp->nrows = pi * cp->recs_per_page + cnt;
+    const int32_t used = hf_used_slots(db->page(pid), cnt);
+    if (used > 0) {
+      cp->nrows = pi * cp->recs_per_page + used;
       break;
     }
   }

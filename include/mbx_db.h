@@ -123,6 +123,16 @@ int mbx_db_purge(mbx_db* db, const char* name);
 int mbx_db_bitmap_write(mbx_db* db, const char* filename, const uint64_t* words, int64_t nwords);
 int mbx_db_bitmap_read(mbx_db* db, const char* filename, uint64_t* words, int64_t nwords_cap, int64_t* nwords_out);
 
+/* btreeExist[col] of cf.hdr, the record Columnarfile.createBTreeIndex updates
+ * (R/columnar/Columnarfile.java:685-686): set != 0 sets it (a same-length
+ * record update in place, no page allocated); *flag (may be NULL) = its value
+ * afterwards.  No B-tree pages are written: the flag is this executor's marker
+ * that `index ... btree` ran, the ordered index itself is rebuilt on the device
+ * from the column (mbx_index_build, include/mbx_index.h), and a DB file that
+ * carries the flag is not a reference-readable B-tree.  mbx_db_columnar_insert
+ * and mbx_db_purge refuse files whose flag is set, as before. */
+int mbx_db_btree_flag(mbx_db* db, const char* name, int32_t col, int32_t set, int32_t* flag);
+
 /* Columnarfile.createBitMapIndex(col) (R/columnar/Columnarfile.java:698-753)
  * on the GPU: distinct live values in first-occurrence order (k_distinct),
  * one BitSet per value (k_index_build4 / k_index_build) over `t` -- the

@@ -1384,6 +1384,23 @@ int find_hdr_record(mbx_db* db, int32_t hdr, int32_t index, uint8_t** rec, int32
 
 }  // namespace
 
+extern "C" int mbx_db_btree_flag(mbx_db* db, const char* name, int32_t col, int32_t set, int32_t* flag) {
+  NOTNULL(db);
+  NOTNULL(name);
+  if (flag) *flag = 0;
+  Schema sc;
+  int rc = read_schema(db, name, &sc);
+  if (rc) return rc;
+  if (col < 0 || col >= sc.ncols) return fail(MBX_E_RANGE, "createBTreeIndex: column %d of %d", col, sc.ncols);
+  uint8_t* rec;
+  int32_t len;
+  if ((rc = find_hdr_record(db, get_file_entry(db, std::string(name) + ".hdr"), 4, &rec, &len))) return rc;
+  if (col >= len) return fail(MBX_E_INVALID, "%s.hdr: btreeExist holds %d columns", name, len);
+  if (set) rec[col] = 1;  // a same-length record update in place: no page is allocated
+  if (flag) *flag = rec[col] == 1;
+  return MBX_OK;
+}
+
 extern "C" int mbx_db_create_bitmap_index(mbx_ctx* c, mbx_db* db, const char* name, const mbx_table* t, int32_t col,
                                           int32_t* nvalues) {
   NOTNULL(c);

@@ -151,8 +151,10 @@ void index_cmd(const std::vector<std::string>& a) {
   const int col = cf.colNameToIndex(a[3]);
   if (a[4] == "bitmap" || a[4] == "BITMAP") {
     cf.createBitMapIndex(col);
+  } else if (a[4] == "btree" || a[4] == "BTREE") {
+    cf.createBTreeIndex(col);  // the device's ordered index + btreeExist[col] in cf.hdr
   } else {
-    throw std::runtime_error("BTREE indexes are not built by the GPU executor (B-tree access path out of scope)");
+    throw std::runtime_error("index type invalid.");
   }
 }
 
@@ -247,7 +249,15 @@ void query(const std::vector<std::string>& a) {
                               t.out_indexes, t.proj, filter, col + 1, false);
     print_rows(is, cf, t);
   } else if (access == "BTREE") {
-    throw std::runtime_error("BTREE access is not part of the GPU path (out of scope)");
+    // Query.executeBtreeScan (R/input/Query.java:198-246)
+    if (!cf.btreeIndexExists(col)) throw std::runtime_error("BTREE index does not exist on column " + parts[0]);
+    e.operand1.symbol = FldSpec(RelSpec(RelSpec::outer), 1);  // the key is field 1
+    e.indexType = IndexType(IndexType::B_Index);
+    const bool index_only = t.out_indexes.size() == 1 && t.out_indexes[0] == col;
+    index::ColumnIndexScan is(IndexType(IndexType::B_Index), &cf, cf.get_fileName() + ".btree." + std::to_string(col),
+                              cf.getAttributeTypes(), cf.getStringSizes(), cf.getFieldCount(), (int)t.proj.size(),
+                              t.out_indexes, t.proj, filter, col + 1, index_only);
+    print_rows(is, cf, t);
   } else {
     throw std::runtime_error("access type invalid.");
   }
@@ -573,7 +583,17 @@ void delete_query(const std::vector<std::string>& a) {
   Cnf cnf{{parts}};
   columnar::BitSetPtr sel;
   if (acc == "BTREE") {
-    throw std::runtime_error("BTREE index does not exist on column " + parts[0]);
+    if (!cf.btreeIndexExists(col)) throw std::runtime_error("BTREE index does not exist on column " + parts[0]);
+    // the B_Index scan's positions (R/input/DeleteQuery.java:105-180)
+    CondExpr e;
+    e.op = AttrOperator::findOperator(parts[1]);
+    set_literal(cf, col, parts[2], e);
+    e.operand1.symbol = FldSpec(RelSpec(RelSpec::outer), 1);
+    e.indexType = IndexType(IndexType::B_Index);
+    CondExpr* filter[2] = {&e, nullptr};
+    index::ColumnIndexScan is(IndexType(IndexType::B_Index), &cf, cf.get_fileName() + ".btree." + std::to_string(col),
+                              cf.getAttributeTypes(), cf.getStringSizes(), cf.getFieldCount(), filter, col + 1);
+    sel = is.getPositionsOfIndexScan();
   } else if (acc == "BITMAP") {
     if (!cf.bitmapIndexExists(col)) throw std::runtime_error("Bitmap index does not exist on column " + parts[0]);
     sel = index_sel(cf, cnf, 0, 1, IndexType::Bitmap);

@@ -239,13 +239,20 @@ struct Columnarfile::Impl {
   std::map<int, std::map<std::string, BitSetPtr>> bitmaps;  // staged BitMapFiles: col -> value key
   BitSetPtr deleted_bm;
   bool deleted_loaded = false;
+  std::map<int, mbx_index*> btrees;  // device ordered indexes of the staged table: col -> index
+  void drop_btrees() {
+    for (auto& kv : btrees) mbx_index_free(kv.second);
+    btrees.clear();
+  }
   void invalidate() {
+    drop_btrees();  // snapshots of the staged table, which is about to be replaced
     bitmaps.clear();
     deleted_bm.reset();
     deleted_loaded = false;
     dirty = true;
   }
   ~Impl() {
+    drop_btrees();
     bitmaps.clear();
     deleted_bm.reset();
     if (table) mbx_table_free(table);
@@ -449,6 +456,34 @@ void Columnarfile::createBitMapIndex(int colNo) {
       mbx_db_create_bitmap_index(global::SystemDefs::ctx(), I.db, I.name.c_str(), table(), colNo, &n),
       "createBitMapIndex");
   I.bitmaps.erase(colNo);
+}
+
+// createBTreeIndex (Columnarfile.java:659-689): the index is the device's
+// sorted (key, position) array; cf.hdr gets btreeExist[col], nothing else
+void Columnarfile::createBTreeIndex(int colNo) {
+  Impl& I = *impl_;
+  if (colNo < 0 || colNo >= (int)I.types.size()) throw chainexception::ChainException("createBTreeIndex: column");
+  btreeIndex(colNo);
+  chk<chainexception::ChainException>(mbx_db_btree_flag(I.db, I.name.c_str(), colNo, 1, nullptr), "createBTreeIndex");
+}
+
+bool Columnarfile::btreeIndexExists(int colNo) const {
+  int32_t flag = 0;
+  chk<chainexception::ChainException>(mbx_db_btree_flag(impl_->db, impl_->name.c_str(), colNo, 0, &flag),
+                                      "btreeIndexExists");
+  return flag != 0;
+}
+
+mbx_index* Columnarfile::btreeIndex(int colNo) const {
+  Impl& I = *impl_;
+  mbx_table* t = table();  // staging first: a changed DB file drops every index
+  auto it = I.btrees.find(colNo);
+  if (it != I.btrees.end()) return it->second;
+  mbx_index* x = nullptr;
+  chk<chainexception::ChainException>(mbx_index_build(global::SystemDefs::ctx(), t, colNo, &x),
+                                      "createBTreeIndex: ordered index of column " + std::to_string(colNo));
+  I.btrees[colNo] = x;
+  return x;
 }
 
 std::vector<std::string> Columnarfile::getBitmapValues(int colNo) const {
@@ -946,12 +981,15 @@ ColumnIndexScan::ColumnIndexScan(IndexType index, columnar::Columnarfile* cf, co
     : f_(cf), colNo_(fldNum - 1), outIndexes_(outIndexes), types_(types), index_only_(indexOnly) {
   (void)indName;
   (void)noInFlds;
-  if (index.indexType != IndexType::Bitmap)
-    throw UnknownIndexTypeException("only the Bitmap branch of ColumnIndexScan runs on the GPU (B-tree: out of scope)");
-  if (!selects || !selects[0]) throw IndexException("ColumnIndexScan: no selection");
+  if (index.indexType != IndexType::Bitmap && index.indexType != IndexType::B_Index)
+    throw UnknownIndexTypeException("Only BTree and Bitmap index is supported so far");
+  btree_ = index.indexType == IndexType::B_Index;
+  if (!btree_ && (!selects || !selects[0])) throw IndexException("ColumnIndexScan: no selection");
   if ((int)outFlds.size() != noOutFlds) throw IndexException("ColumnIndexScan: noOutFlds");
-  sel_ = *selects[0];
-  sel_.next = nullptr;
+  if (selects && selects[0]) {
+    sel_ = *selects[0];
+    sel_.next = nullptr;
+  }
   std::vector<AttrType> otypes;
   std::vector<short> osizes;
   const auto sizes = cf->getAttrSizes();
@@ -961,6 +999,18 @@ ColumnIndexScan::ColumnIndexScan(IndexType index, columnar::Columnarfile* cf, co
   }
   (void)str_sizes;
   Jtuple_.setHdr(otypes, osizes);
+  if (btree_) {
+    // the selection's symbol is field 1 of the (key) tuple: map it to the key column
+    cnf_ = iterator::flatten(selects, 1, colNo_ + 1);
+    cnf_strs_.reserve(2 * cnf_.conds.size());  // no reallocation: the operands point into it
+    for (mbx_condexpr& c : cnf_.conds)
+      for (mbx_operand* o : {&c.operand1, &c.operand2})
+        if (o->type == AttrType::attrString) {
+          cnf_strs_.emplace_back(o->string ? std::string(o->string, (size_t)o->string_len) : std::string());
+          o->string = cnf_strs_.back().data();
+        }
+    return;
+  }
   values_ = valueBitmaps(*cf, colNo_, sel_);
 }
 
@@ -970,12 +1020,46 @@ ColumnIndexScan::ColumnIndexScan(IndexType index, columnar::Columnarfile* cf, co
     : ColumnIndexScan(index, cf, indName, types, str_sizes, noInFlds, 0, {}, {}, selects, fldNum, false) {}
 
 BitSetPtr ColumnIndexScan::getPositionsOfIndexScan() {
+  if (!positions_ && btree_) {
+    // the scan's positions as a BitSet (the order is the cursor's, not the BitSet's)
+    const int64_t nbits = f_->positions();
+    std::vector<int64_t> ids((size_t)(nbits > 0 ? nbits : 1));
+    int64_t n = 0;
+    const mbx_cnf cnf = cnf_.view();
+    chk<IndexException>(mbx_index_scan_positions(global::SystemDefs::ctx(), f_->table(), f_->btreeIndex(colNo_), &cnf,
+                                                 ids.data(), nbits, &n),
+                        "ColumnIndexScan: B_Index positions");
+    std::vector<uint64_t> words((size_t)((nbits + 63) / 64) + 1, 0);
+    for (int64_t k = 0; k < n; k++) words[(size_t)(ids[(size_t)k] >> 6)] |= 1ull << (ids[(size_t)k] & 63);
+    mbx_bitmap* b = nullptr;
+    chk<IndexException>(mbx_bitmap_upload(global::SystemDefs::ctx(), nbits, words.data(), &b),
+                        "ColumnIndexScan: B_Index positions");
+    positions_ = std::make_shared<columnar::DeviceBitSet>(b);
+  }
   if (!positions_) positions_ = or_bitmaps(*f_, {values_});
   return positions_;
 }
 
 void ColumnIndexScan::open_cursor() {
   if (rows_.open()) return;
+  if (btree_) {
+    // index_only delivers the key itself: the key column projected
+    const std::vector<int> cols = index_only_ ? std::vector<int>{colNo_} : outIndexes_;
+    std::vector<int32_t> pc(cols.begin(), cols.end());
+    const mbx_cnf cnf = cnf_.view();
+    mbx_cursor* c = nullptr;
+    chk<IndexException>(mbx_index_scan_open(global::SystemDefs::ctx(), f_->table(), f_->btreeIndex(colNo_), &cnf,
+                                            pc.data(), (int32_t)pc.size(), &c),
+                        "ColumnIndexScan: B_Index scan");
+    if (index_only_) {
+      std::vector<AttrType> t{types_.at((size_t)colNo_)};
+      std::vector<short> s;
+      if (t[0].attrType == AttrType::attrString) s.push_back(f_->getAttrSizes()[(size_t)colNo_]);
+      Jtuple_.setHdr(t, s);
+    }
+    rows_.reset(c, f_->getAttributeTypes(), f_->getAttrSizes(), pc);
+    return;
+  }
   const std::vector<int> cols = index_only_ ? std::vector<int>{} : outIndexes_;
   std::vector<int32_t> pc(cols.begin(), cols.end());
   rows_.reset(cnf_cursor(*f_, {values_}, cols, "ColumnIndexScan"), f_->getAttributeTypes(), f_->getAttrSizes(), pc);
@@ -984,7 +1068,7 @@ void ColumnIndexScan::open_cursor() {
 heap::Tuple* ColumnIndexScan::get_next() {
   open_cursor();
   if (!rows_.next()) return nullptr;
-  if (index_only_) {
+  if (index_only_ && !btree_) {
     // only the key is returned (R/index/ColumnIndexScan.java:512-565)
     std::vector<AttrType> t{types_.at((size_t)colNo_)};
     std::vector<short> s;
@@ -1010,8 +1094,11 @@ void ColumnIndexScan::close() {
   rows_.close();
   closeFlag = true;
 }
-// nor does ColumnIndexScan (R/index/ColumnIndexScan.java:28-740): Iterator's no-op and -1
-void ColumnIndexScan::restart() {}
+// nor does ColumnIndexScan (R/index/ColumnIndexScan.java:28-740): Iterator's no-op and -1;
+// the B_Index branch starts its cursor over
+void ColumnIndexScan::restart() {
+  if (btree_) rows_.restart();
+}
 int ColumnIndexScan::getTupleSize() { return -1; }
 
 ColumnarIndexScan::ColumnarIndexScan(columnar::Columnarfile* cf, const std::vector<int>& fldNums,

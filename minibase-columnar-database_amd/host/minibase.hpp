@@ -28,6 +28,7 @@
 
 #include "../../include/mbx.h"
 #include "../../include/mbx_db.h"
+#include "../../include/mbx_index.h"
 #include "../../include/mbx_sort.h"
 
 // Everything lives in `minibase::` (the Java packages become nested
@@ -281,6 +282,12 @@ class Columnarfile {
   bool bitmapIndexExists(int colNo) const;
   std::vector<std::string> getBitmapValues(int colNo) const;  // registered value keys
   BitSetPtr getBitmapIndex(int colNo, const std::string& key) const;  // empty BitSet if absent
+  // ordered index (createBTreeIndex :659-689; include/mbx_index.h): the index
+  // lives on the device, cached per column beside the staged table; the DB
+  // file only carries btreeExist[col] (no B-tree pages are written)
+  void createBTreeIndex(int colNo);
+  bool btreeIndexExists(int colNo) const;
+  mbx_index* btreeIndex(int colNo) const;  // built on first use after a change
   BitSetPtr getMarkedDeleted() const;  // may be null (nothing deleted)
   void markTupleDeleted(int64_t position);
   void invalidate();  // the DB file changed under this object: re-stage on next use
@@ -473,8 +480,11 @@ class UnknownIndexTypeException : public chainexception::ChainException {
   using ChainException::ChainException;
 };
 
-// R/index/ColumnIndexScan.java:76-272 (Bitmap branch): `col op literal`
-// over the bitmap indexes; positions skip deleted rows.
+// R/index/ColumnIndexScan.java:76-272.  Bitmap branch: `col op literal`
+// over the bitmap indexes; positions skip deleted rows.  B_Index branch
+// (:309-494): the ordered index's scan (mbx_index_scan_open) -- the selection's
+// symbol is field 1 of the key tuple, mapped to the key column as
+// ColumnarColumnScan does; rows come in (key, position) order.
 class ColumnIndexScan : public iterator::Iterator {
  public:
   ColumnIndexScan(IndexType index, columnar::Columnarfile* cf, const std::string& indName,
@@ -506,6 +516,9 @@ class ColumnIndexScan : public iterator::Iterator {
   std::vector<int> outIndexes_;
   std::vector<AttrType> types_;
   bool index_only_ = false;
+  bool btree_ = false;
+  iterator::CnfImage cnf_;            // B_Index: the whole selection, field 1 -> the key column
+  std::vector<std::string> cnf_strs_;  // its string literals (owned)
   CondExpr sel_{};
   std::vector<columnar::BitSetPtr> values_;  // the value bitmaps OR-ed by getBitSet
   columnar::BitSetPtr positions_;            // their OR minus deleted, built on first use

@@ -112,16 +112,20 @@ EXPORTS = [
     "mbx_db_columnar_insert", "mbx_db_columnar_info", "mbx_db_mark_deleted", "mbx_db_bitmap_write",
     "mbx_db_bitmap_read", "mbx_db_stage", "mbx_db_allocate_pages", "mbx_db_add_file_entry",
     "mbx_db_create_bitmap_index", "mbx_db_bitmap_values", "mbx_db_bitmap_stage", "mbx_db_mark_deleted_many",
-    "mbx_db_purge", "mbx_db_stage_range", "mbx_db_bitmap_stage_range",
+    "mbx_db_purge", "mbx_db_stage_range", "mbx_db_bitmap_stage_range", "mbx_db_btree_flag",
     # include/mbx_join.h
     "mbx_join", "mbx_join_info", "mbx_join_fetch", "mbx_join_free", "mbx_gather",
     "mbx_join_equi_conj", "mbx_join_with", "mbx_join_result_form",
     # include/mbx_sort.h
     "mbx_sort", "mbx_sort_info", "mbx_sort_fetch", "mbx_sort_free",
+    # include/mbx_index.h
+    "mbx_index_build", "mbx_index_info", "mbx_index_free", "mbx_index_key_ranges", "mbx_index_probe",
+    "mbx_index_scan_open", "mbx_index_scan_positions",
 ]
 JOIN_BMJ, JOIN_NLJ = 0, 1
 JOIN_FORM_AUTO, JOIN_FORM_MATRIX, JOIN_FORM_EQUI = 0, 1, 2
 SORT_ASC, SORT_DSC = 0, 1
+MAX_KEY_RANGES = 33  # MBX_INDEX_MAX_RANGES
 
 
 class JoinTerm(ctypes.Structure):
@@ -131,6 +135,12 @@ class JoinTerm(ctypes.Structure):
 
 class SortKey(ctypes.Structure):
     _fields_ = [("col", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class KeyRange(ctypes.Structure):
+    """mbx_key_range (include/mbx_index.h)."""
+    _fields_ = [("lo_cond", ctypes.c_int32), ("lo_strict", ctypes.c_int32), ("hi_cond", ctypes.c_int32),
+                ("hi_strict", ctypes.c_int32)]
 
 
 class JoinCnf(ctypes.Structure):
@@ -291,6 +301,7 @@ def lib():
         "mbx_db_bitmap_stage": ([V, V, ctypes.c_char_p, I64, P(V)], ctypes.c_int),
         "mbx_db_mark_deleted_many": ([V, ctypes.c_char_p, V, I64], ctypes.c_int),
         "mbx_db_purge": ([V, ctypes.c_char_p], ctypes.c_int),
+        "mbx_db_btree_flag": ([V, ctypes.c_char_p, I32, I32, P(I32)], ctypes.c_int),
         "mbx_db_stage_range": ([V, V, ctypes.c_char_p, I64, I64, P(V)], ctypes.c_int),
         "mbx_db_bitmap_stage_range": ([V, V, ctypes.c_char_p, I64, I64, P(V)], ctypes.c_int),
         "mbx_join": ([V, V, V, V, V, P(JoinCnf), I32, I64, P(V)], ctypes.c_int),
@@ -305,6 +316,13 @@ def lib():
         "mbx_sort_info": ([V, P(I64), P(I32), P(I32)], ctypes.c_int),
         "mbx_sort_fetch": ([V, V, I64, I64, V], ctypes.c_int),
         "mbx_sort_free": ([V], ctypes.c_int),
+        "mbx_index_build": ([V, V, I32, P(V)], ctypes.c_int),
+        "mbx_index_info": ([V, P(I64), P(I32), P(I32)], ctypes.c_int),
+        "mbx_index_free": ([V], ctypes.c_int),
+        "mbx_index_key_ranges": ([P(ColDesc), P(Cnf), I32, P(KeyRange), I32, P(I32)], ctypes.c_int),
+        "mbx_index_probe": ([V, V, P(Cnf), P(I32), P(I64)], ctypes.c_int),
+        "mbx_index_scan_open": ([V, V, V, P(Cnf), P(I32), I32, P(V)], ctypes.c_int),
+        "mbx_index_scan_positions": ([V, V, V, P(Cnf), V, I64, P(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -400,7 +418,7 @@ class Context:
         if self.h:
             # cursors and bitmaps first, then plans, then tables
             order = {"mbx_graph_free": -2, "mbx_comm_free": -1, "mbx_cursor_close": 0, "mbx_bitmap_free": 1,
-                     "mbx_plan_free": 2, "mbx_table_free": 3}
+                     "mbx_plan_free": 2, "mbx_index_free": 2, "mbx_table_free": 3}
             for ch in sorted(list(self._children), key=lambda o: order.get(o._free, 9)):
                 ch.close()
             lib().mbx_free(self.h)
@@ -578,6 +596,50 @@ class Context:
             return (pos[:n.value], pr.value, pt.value) if info else pos[:n.value]
         finally:
             lib().mbx_sort_free(h)
+
+    # -- ordered column index: BTREE access (include/mbx_index.h) ----------
+    def index_btree(self, table, col):
+        """mbx_index_build: the ordered (key, position) index of column `col`
+        (Columnarfile.createBTreeIndex), a snapshot of the column."""
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_index_build(self.h, table.h, col, ctypes.byref(h)))
+        return Index(self, h, table, col)
+
+    def index_probe(self, index, cnf):
+        """mbx_index_probe: (key intervals, index entries in them) -- the
+        searches of a scan alone."""
+        keep = []
+        c = make_cnf(cnf, keep)
+        nr, ne = ctypes.c_int32(), ctypes.c_int64()
+        _chk(lib().mbx_index_probe(self.h, index.h, ctypes.byref(c), ctypes.byref(nr), ctypes.byref(ne)))
+        return nr.value, ne.value
+
+    def index_scan(self, index, cnf, proj=()):
+        """mbx_index_scan_open: the B_Index ColumnIndexScan as a Cursor -- rows
+        in (key, position) order."""
+        keep = []
+        c = make_cnf(cnf, keep)
+        pj = (ctypes.c_int32 * max(1, len(proj)))(*proj)
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_index_scan_open(self.h, index.table.h, index.h, ctypes.byref(c), pj, len(proj),
+                                       ctypes.byref(h)))
+        return Cursor(self, h, index.table, list(proj))
+
+    def index_positions(self, index, cnf, cap=None):
+        """mbx_index_scan_positions: the scan's global positions in index order."""
+        keep = []
+        c = make_cnf(cnf, keep)
+        cap = index.table.nrows if cap is None else cap
+        ids = np.zeros(max(1, cap), dtype=np.int64)
+        n = ctypes.c_int64()
+        _chk(lib().mbx_index_scan_positions(self.h, index.table.h, index.h, ctypes.byref(c), ids.ctypes.data, cap,
+                                            ctypes.byref(n)))
+        return ids[:n.value]
+
+    @staticmethod
+    def index_key_ranges(key_desc, cnf, key_fld=1):
+        """mbx_index_key_ranges (the module function of the same name)."""
+        return index_key_ranges(key_desc, cnf, key_fld)
 
     def gather(self, table, positions, proj):
         pos = np.ascontiguousarray(positions, dtype=np.int64)
@@ -767,7 +829,11 @@ class Context:
                                              None if deleted is None else deleted.h, pj, len(proj), dev_ids,
                                              outs, dev_count))
 
-    def index_build(self, table, col, values):
+    def index_build(self, table, col, values=None):
+        """values: one BitSet per value (mbx_bitmap_index_build); without
+        values: the ordered index of the column (index_btree)."""
+        if values is None:
+            return self.index_btree(table, col)
         keep = []
         ops = (Operand * len(values))(*[_operand(v, keep) for v in values])
         hs = (ctypes.c_void_p * len(values))()
@@ -865,6 +931,22 @@ def count_frame_decode(frame):
 def count_frame_fits(nblocks, nranks):
     """mbx_count_frame_fits: nranks frames of <= nblocks-block scans sum exactly."""
     return bool(lib().mbx_count_frame_fits(int(nblocks), int(nranks)))
+
+
+def index_key_ranges(key_desc, cnf, key_fld=1):
+    """mbx_index_key_ranges: the key intervals a B_Index scan of `cnf` reads on
+    a key column key_desc = (attr_type, size), as a list of (lo_cond,
+    lo_strict, hi_cond, hi_strict) in ascending key order; an end's cond is
+    the index of the flattened CNF term whose literal bounds it, -1:
+    unbounded.  Needs no GPU."""
+    keep = []
+    c = make_cnf(cnf, keep)
+    d = ColDesc(key_desc[0], key_desc[1])
+    cap = MAX_KEY_RANGES
+    out = (KeyRange * cap)()
+    n = ctypes.c_int32()
+    _chk(lib().mbx_index_key_ranges(ctypes.byref(d), ctypes.byref(c), key_fld, out, cap, ctypes.byref(n)))
+    return [(out[i].lo_cond, out[i].lo_strict, out[i].hi_cond, out[i].hi_strict) for i in range(n.value)]
 
 
 def bitslice_range(kmin, kmax):
@@ -1008,6 +1090,22 @@ class Table(_Handle):
         if t == STRING:
             return np.zeros((n, size), dtype=np.uint8)
         return np.zeros(n, dtype=np.int32 if t == INTEGER else np.float32)
+
+
+class Index(_Handle):
+    """mbx_index: the ordered (key, position) index of one column."""
+    _free = "mbx_index_free"
+
+    def __init__(self, ctx, h, table, col):
+        self.ctx, self.h, self.table, self.col = ctx, h, table, col
+        ctx._own(self)
+
+    def info(self):
+        """mbx_index_info: {"entries", "col", "last_fast_path"} -- the last
+        scan's path: 1 no deleted image, 0 the ordered filter, -1 none yet."""
+        n, c, f = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        _chk(lib().mbx_index_info(self.h, ctypes.byref(n), ctypes.byref(c), ctypes.byref(f)))
+        return {"entries": n.value, "col": c.value, "last_fast_path": f.value}
 
 
 class Plan(_Handle):
@@ -1174,6 +1272,12 @@ class Db:
     def purge(self, name):
         """Columnarfile.purgeAllDeletedTuples."""
         _chk(lib().mbx_db_purge(self.h, name.encode()))
+
+    def btree_flag(self, name, col, set=False):
+        """mbx_db_btree_flag: btreeExist[col] of cf.hdr, set first when asked."""
+        f = ctypes.c_int32()
+        _chk(lib().mbx_db_btree_flag(self.h, name.encode(), col, 1 if set else 0, ctypes.byref(f)))
+        return bool(f.value)
 
     def bitmap_write(self, filename, words):
         w = np.ascontiguousarray(words, dtype=np.uint64)

@@ -791,12 +791,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 // the block's exact reduction thread m < members works count_m out of the
 // block's totals and hands it in as member m's own launch would: its ticket
 // area (that of its position in the chain), count word or frame, nan_out.
+// A group's record is all a block reads before its first plane load, the launch's
+// nb included: one round of scalar loads and one wait, as in k_scan_bits1.
 struct Bits1Group {
   int64_t nrows;
   int32_t tiles_per_block;
   uint16_t first, count;               // its members: m[first, first + count)
   const uint32_t* pl[kSliceMaxTerms];
   const uint64_t* deleted;             // device or null
+  uint32_t nb;                         // blocks per group: the same in every record of a launch
+  uint32_t pad_;
 };
 struct Bits1Member {
   int64_t* out;      // the count word (kPlaneFinPacked) / the count frame (kPlaneFinFrame)
@@ -808,11 +812,9 @@ struct Bits1Member {
 struct Bits1Shared {
   Bits1Group g[kMaxFuse];   // what the first plane load needs
   Bits1Member m[kMaxFuse];  // in group order
-  uint32_t nb;              // blocks per group
-  uint32_t pad_;
 };
-static_assert(sizeof(Bits1Group) == 56 && sizeof(Bits1Member) == 32, "k_scan_bits1_shared's records");
-static_assert(sizeof(Bits1Shared) == kMaxFuse * 88 + 8 && sizeof(Bits1Shared) <= 4096, "the groups fit the kernel arguments");
+static_assert(sizeof(Bits1Group) == 64 && sizeof(Bits1Member) == 32, "k_scan_bits1_shared's records");
+static_assert(sizeof(Bits1Shared) == kMaxFuse * 96 && sizeof(Bits1Shared) <= 4096, "the groups fit the kernel arguments");
 
 constexpr int bits1_top_plane(int s) { return s >= 8 ? 3 : (s >= 4 ? 2 : (s >= 2 ? 1 : 0)); }
 
@@ -835,21 +837,46 @@ template <int NP, bool DEL, int FIN>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NP >= 4 ? 4 : 8, 8))) void k_scan_bits1_shared(
     Bits1Shared S) {
   static_assert(NP >= 1 && NP <= kSliceMaxTerms, "a chain without planes stays one grid row per query");
-  if (blockIdx.x >= S.nb) return;
-  const Bits1Group& P = S.g[blockIdx.y];
   constexpr int kB = bits1_batch(NP, DEL);
   constexpr int kM = 1 << NP;
   constexpr int kTileDwords = kBitTileRows / 32;
-  const uint32_t nblocks = S.nb;
+  // Group blockIdx.y's record, held in scalar registers from here on: every scalar load of the
+  // kernel is issued above the padding-block branch (the record of a valid blockIdx.y is always
+  // readable) and the first plane load waits for them once.  With nb a field of its own behind the
+  // records, hipcc loaded it, waited and branched, and only then loaded the record: a second round
+  // trip to cold kernel-argument lines in front of every block's first plane byte.
+  const Bits1Group& G = S.g[blockIdx.y];
+  struct {
+    int64_t nrows;
+    int32_t tiles_per_block;
+    const uint32_t* pl[NP];
+    const uint64_t* deleted;
+    uint32_t first, count;
+  } P;
+  P.nrows = G.nrows;
+  P.tiles_per_block = G.tiles_per_block;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) P.pl[k] = G.pl[k];
+  P.deleted = G.deleted;
+  uint32_t fc;  // first, count: 16 bits each
+  __builtin_memcpy(&fc, &G.first, sizeof(fc));
+  uint32_t nblocks = G.nb;
+  asm volatile("" : "+s"(P.nrows), "+s"(P.tiles_per_block), "+s"(fc), "+s"(nblocks));
+#pragma unroll
+  for (int k = 0; k < NP; ++k) asm volatile("" : "+s"(P.pl[k]));
+  if constexpr (DEL) asm volatile("" : "+s"(P.deleted));
+  if (blockIdx.x >= nblocks) return;
+  P.first = fc & 0xFFFFu;
+  P.count = fc >> 16;
   const int lane = threadIdx.x & 63;
   const int wave = (int)uniform(threadIdx.x >> 6);
-  const int members = P.count;
+  const int members = (int)P.count;
   // Thread m's member record is a vector load from the kernel arguments (threads past the group's
   // members read its last one and drop it), issued after the last tile.  Left alone, hipcc sinks it
   // below the barrier, a whole round trip on the block's tail; member_pin holds it above the barrier
   // and waits for it there, so the block's reduction covers most of the trip.  (Issued before the
   // first plane load it costs that load a wait: hipcc settles every pending load at the loop's head.)
-  const Bits1Member& Mr = S.m[P.first + min((int)threadIdx.x, members - 1)];
+  const Bits1Member& Mr = S.m[(int)P.first + min((int)threadIdx.x, members - 1)];
   uint64_t out = 0, ticket = 0, nan_out = 0;
   uint32_t table = 0;
   int32_t groups = 0;
@@ -1166,6 +1193,8 @@ static int bits1_fuse_groups(Bits1Fuse* f, int n, int* shared) {
       G.count = 0;
       for (int k = 0; k < kSliceMaxTerms; ++k) G.pl[k] = q.pl[k];
       G.deleted = q.deleted;
+      G.nb = f->gx;
+      G.pad_ = 0;
     }
     S.g[g].count += 1;
     of[j] = g;
@@ -1181,8 +1210,6 @@ static int bits1_fuse_groups(Bits1Fuse* f, int n, int* shared) {
         S.m[at++] = Bits1Member{q.out, q.ticket, q.nan_out, q.table, q.ticket_groups};
       }
   }
-  S.nb = f->gx;
-  S.pad_ = 0;
   return ng;
 }
 

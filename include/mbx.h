@@ -201,7 +201,10 @@ int mbx_table_group(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t nco
  * return the snapshot's counts (and a HIP graph captured before a drop must
  * not be replayed after it).  Naming a column that is already sliced
  * rebuilds it.  A drop or rebuild unbinds every plan compiled before it:
- * their COUNT scans read the live columns again (no allocation at launch). */
+ * their COUNT scans read the live columns again (no allocation at launch).
+ * The int32 code column of a dictionary (mbx_table_dict, mbx_dict.h) is sliced
+ * by mbx_plan_compile only; naming its char(n) column here stays MBX_E_TYPE,
+ * and ncols = 0 drops the code columns' planes with every other slice. */
 int mbx_table_slice(mbx_ctx *ctx, mbx_table *t, const int32_t *cols, int32_t ncols);
 /* *stored_planes = the planes column `col` keeps (1..4), 0: not sliced */
 int mbx_table_slice_info(const mbx_table *t, int32_t col, int32_t *stored_planes);
@@ -260,7 +263,14 @@ int mbx_bitslice_bound(uint32_t kmin, uint32_t kmax, uint32_t key, int32_t upper
  * BitSet scans read the live columns again.
  * Other plans, plans compiled under a capture while planes are missing, and
  * plans whose bit planes cannot be allocated take the byte planes;
- * auto_bitslice = 0 binds every plan as if there were no bit planes. */
+ * auto_bitslice = 0 binds every plan as if there were no bit planes.
+ * Dictionaries (mbx_dict.h): a char(n) column that has a dictionary when the
+ * plan is compiled, and that the plan names only in `column OP string-literal`
+ * terms, is read through its int32 codes -- each such term becomes an int
+ * range term on the code column (mbx_dict_term_range; mbx_plan_dict_terms
+ * counts them), the code column counts as an int32 column for everything
+ * above, and the plan shares ownership of the dictionary it was compiled on.
+ * Compiling never builds a dictionary. */
 int mbx_plan_compile(mbx_ctx *ctx, const mbx_table *t, const mbx_cnf *cnf, mbx_plan **out);
 int mbx_plan_free(mbx_plan *p);
 /* *sliced = 1 when COUNT launches of this plan currently take the sliced

@@ -1,12 +1,13 @@
 // mbx_objects.hpp -- host-side objects behind the opaque handles of
 // include/mbx.h and include/mbx_db.h, shared by the C-ABI's files (mbx_api.cpp,
-// mbx_table.cpp, mbx_plan.cpp, mbx_scan.cpp, mbx_bitmap.cpp, mbx_cursor.cpp)
-// and mbx_db.cpp (Minibase DB files).  Not part of the C-ABI.
+// mbx_table.cpp, mbx_plan.cpp, mbx_scan.cpp, mbx_bitmap.cpp, mbx_cursor.cpp,
+// mbx_dict.cpp) and mbx_db.cpp (Minibase DB files).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <deque>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -158,12 +159,42 @@ struct TSlice {
   uint32_t* bdev = nullptr;
 };
 
+// The order-preserving dictionary of one char(n) column (mbx_table_dict,
+// include/mbx_dict.h): a snapshot shared by the table and by every plan
+// compiled on it, freed with its last owner (the device is set by whoever
+// lets go of it: mbx_table_dict, mbx_table_free, mbx_plan_free).
+struct TDict {
+  int32_t col = 0;               // the table column it encodes
+  int32_t size = 0;              // char(size)
+  int64_t nvalues = 0;
+  std::vector<uint8_t> values;   // host: the distinct values ascending, caller layout (nvalues x size bytes)
+  uint32_t* dvalues = nullptr;   // device: their string images (nvalues x stride_w words)
+  TCol codes;                    // the int32 code column: codes.dev[row] = rank of the row's value; owned
+  mutable TSlice slice;          // planes of the code column, built on demand as mbx_table::slices are
+  TDict() = default;
+  TDict(const TDict&) = delete;
+  TDict& operator=(const TDict&) = delete;
+  ~TDict() {
+    hipFree(dvalues);
+    hipFree(codes.dev);
+    hipFree(slice.dev);
+    hipFree(slice.bdev);
+  }
+};
+
+// A plan names the columns it reads (mbx_plan::slot_col) by table column, or,
+// for a column it reads through its dictionary, by kCodeCol | table column:
+// the code column of the snapshot the plan holds (mbx::plan_col, plan_slice).
+constexpr int32_t kCodeCol = 1 << 30;
+
 struct mbx_table {
   mbx_ctx* ctx = nullptr;
   int64_t nrows = 0;
   int64_t row_offset = 0;
   std::vector<TCol> cols;
   std::vector<TGroup> groups;  // owned
+  // dictionaries (mbx_table_dict): empty, or one entry per column (null: none)
+  std::vector<std::shared_ptr<TDict>> dicts;
   // derived layout built on demand by mbx_plan_compile (which takes a const
   // table): one entry per column, owned.  slice_gen counts drops / rebuilds; a
   // plan bound to an older generation scans the columns.
@@ -209,7 +240,11 @@ struct mbx_plan {
   mbx_ctx* ctx = nullptr;
   const mbx_table* t = nullptr;
   KPlan host{};
-  std::vector<int32_t> slot_col;  // table column of each slot
+  std::vector<int32_t> slot_col;  // table column of each slot, or kCodeCol | column: its code column
+  // the dictionary snapshots the plan reads (shared with the table until it
+  // drops or rebuilds them) and how many of the plan's terms read codes
+  std::vector<std::shared_ptr<TDict>> dicts;
+  int32_t dict_terms = 0;
   bool all_literal = true;        // every term is `column OP literal`
   bool str_lit_fits16 = true;     // every string literal is <= 16 bytes
   // one per aggregate column scanned so far, uploaded on demand by the scan
@@ -273,6 +308,10 @@ int col_kind(int32_t attr);
 // plan_variant: the uploaded one, uploading it first when missing
 int variant_layout(const mbx_plan* p, int32_t agg_col, PlanVariant& v, KPlan* kp_out);
 const PlanVariant* find_variant(const mbx_plan* p, int32_t agg_col);
+// the TCol / the TSlice of a plan column (a slot_col entry): the table's, or
+// for kCodeCol | column those of the plan's dictionary snapshot
+const TCol& plan_col(const mbx_plan* p, int32_t col);
+TSlice& plan_slice(const mbx_plan* p, int32_t col);
 int plan_variant(const mbx_plan* p, int32_t agg_col, const PlanVariant** out);
 // mbx_bitmap.cpp: checks a CNF over bitmaps of nbits bits and fills *C
 int cnf_args(int64_t nbits, const mbx_bitmap* const* bms, const int32_t* conj_offsets, int32_t nconj,

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 
+#include "../../include/mbx_dict.h"
 #include "mbx_objects.hpp"  // with include/mbx.h, the HIP runtime and mbx_internal.hpp
 
 using namespace mbx;
@@ -20,11 +21,26 @@ using namespace mbx;
 
 int mbx::col_kind(int32_t attr) { return attr == MBX_ATTR_INTEGER ? kInt : (attr == MBX_ATTR_REAL ? kReal : kStr); }
 
+// the dictionary snapshot a plan holds for table column `col` (null: none)
+static TDict* plan_dict(const mbx_plan* p, int32_t col) {
+  for (const auto& d : p->dicts)
+    if (d->col == col) return d.get();
+  return nullptr;
+}
+
+const TCol& mbx::plan_col(const mbx_plan* p, int32_t col) {
+  return col & kCodeCol ? plan_dict(p, col & ~kCodeCol)->codes : p->t->cols[(size_t)col];
+}
+
+TSlice& mbx::plan_slice(const mbx_plan* p, int32_t col) {
+  return col & kCodeCol ? plan_dict(p, col & ~kCodeCol)->slice : p->t->slices[(size_t)col];
+}
+
 static int slot_for(mbx_plan* p, int32_t col) {
   for (size_t s = 0; s < p->slot_col.size(); s++)
     if (p->slot_col[s] == col) return (int)s;
   if ((int)p->slot_col.size() >= kMaxCols) return -1;
-  const TCol& tc = p->t->cols[(size_t)col];
+  const TCol& tc = plan_col(p, col);
   const int s = (int)p->slot_col.size();
   p->slot_col.push_back(col);
   p->host.cols[s].base = tc.dev;
@@ -159,6 +175,30 @@ static void str_range_of(KTerm& kt) {
   }
 }
 
+// `code OP literal` for a term that reads a dictionary column through its
+// codes: mbx_dict_term_range's range of codes, and the int compare with the
+// same truth table on the codes 0 .. n-1 for the kernels that evaluate kt.op
+// against kt.ilit
+static void code_term_of(KTerm& kt, int64_t n, int32_t lo, int32_t hi, int32_t neg) {
+  kt.kind = kInt;
+  if (neg) {
+    kt.op = kNE;  // the literal is a value: its one code, negated
+    kt.ilit = lo;
+  } else if (lo > hi) {
+    kt.op = kNever;
+  } else if (lo <= 0) {
+    kt.op = kLE;  // the codes up to hi (hi >= n - 1: every code)
+    kt.ilit = hi;
+  } else if (hi >= n - 1) {
+    kt.op = kGE;
+    kt.ilit = lo;
+  } else {
+    kt.op = kEQ;  // distinct values: an inner range is one code
+    kt.ilit = lo;
+  }
+  set_key_range(kt, lo, hi, neg != 0, 0);
+}
+
 static int compile_into(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_plan* p) {
   p->ctx = c;
   p->t = t;
@@ -169,6 +209,18 @@ static int compile_into(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_
   if (nconj < 0) return fail(MBX_E_INVALID, "plan: nconj = %d", nconj);
   if (nconj > MBX_MAX_CONJ) return fail(MBX_E_UNSUPPORTED, "plan: %d conjuncts (max %d)", nconj, MBX_MAX_CONJ);
   if (nconj > 0 && (!cnf->conds || !cnf->conj_offsets)) return fail(MBX_E_INVALID, "plan: null conds/conj_offsets");
+  // Dictionary columns (mbx_table_dict) are read through their codes unless a
+  // column-vs-column term names them: such a column keeps its strings for all
+  // its terms.  The plan shares the snapshots it reads.
+  std::vector<char> by_code((size_t)ncols, 0);
+  for (int32_t j = 0; j < ncols && !t->dicts.empty(); j++) by_code[(size_t)j] = t->dicts[(size_t)j] != nullptr;
+  for (int32_t k = 0; !t->dicts.empty() && nconj > 0 && k < cnf->conj_offsets[nconj]; k++) {
+    const mbx_operand& o1 = cnf->conds[k].operand1;
+    const mbx_operand& o2 = cnf->conds[k].operand2;
+    if (o1.type != MBX_ATTR_SYMBOL || o2.type != MBX_ATTR_SYMBOL) continue;
+    if (o1.fld >= 1 && o1.fld <= ncols) by_code[(size_t)o1.fld - 1] = 0;
+    if (o2.fld >= 1 && o2.fld <= ncols) by_code[(size_t)o2.fld - 1] = 0;
+  }
   uint32_t all = 0;
   int32_t nterms = 0, pool_used = 0;
   for (int32_t ci = 0; ci < nconj; ci++) {
@@ -256,7 +308,9 @@ static int compile_into(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_
         coln = &o2;  // literal on the left: compare column with literal, operator mirrored
         op = flip(op);
       }
-      const int s1 = slot_for(p, coln->fld - 1);
+      const bool coded = kt.rhs < 0 && ctype == MBX_ATTR_STRING && by_code[(size_t)coln->fld - 1];
+      if (coded && !plan_dict(p, coln->fld - 1)) p->dicts.push_back(t->dicts[(size_t)coln->fld - 1]);
+      const int s1 = slot_for(p, coded ? kCodeCol | (coln->fld - 1) : coln->fld - 1);
       if (s1 < 0) return fail(MBX_E_UNSUPPORTED, "plan: more than %d distinct columns", kMaxCols);
       kt.lhs = s1;
       kt.op = op;
@@ -268,6 +322,14 @@ static int compile_into(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_
         } else if (real) {
           kt.flit = lit->real;
           float_range_of(kt);
+        } else if (coded) {
+          // the literal takes no pool words: the term is an int term on the codes
+          const TDict* d = plan_dict(p, coln->fld - 1);
+          int32_t lo, hi, neg;
+          int rc = mbx_dict_term_range(d->values.data(), d->nvalues, d->size, e.op, lit->string, lit->string_len,
+                                       coln == &o2, &lo, &hi, &neg);
+          if (rc) return rc;
+          code_term_of(kt, d->nvalues, lo, hi, neg);
         } else {
           int rc = add_pool_string(p, *lit, pool_used, kt);
           if (rc) return rc;
@@ -289,6 +351,8 @@ static int compile_into(mbx_ctx* c, const mbx_table* t, const mbx_cnf* cnf, mbx_
     all |= 1u << ci;  // an empty conjunct stays required and is never satisfied
   }
   for (int32_t i = 0; i < nterms; i++) p->host.terms[i].req_below = all & (p->host.terms[i].conj_bit - 1u);
+  for (int32_t i = 0; i < nterms; i++)
+    if (p->slot_col[(size_t)p->host.terms[i].lhs] & kCodeCol) p->dict_terms++;
   p->host.nterms = nterms;
   p->host.all_conj = all;
   return MBX_OK;
@@ -327,7 +391,7 @@ int mbx::variant_layout(const mbx_plan* p, int32_t agg_col, PlanVariant& v, KPla
   bool fast = p->all_literal && p->str_lit_fits16 && p->t->aligned16 && !p->ctx->tune.force_generic;
   std::vector<int> four, wide;
   for (size_t i = 0; i < slots.size(); i++) {
-    const TCol& tc = p->t->cols[slots[i]];
+    const TCol& tc = plan_col(p, slots[i]);
     if (tc.attr_type != MBX_ATTR_STRING) four.push_back((int)i);
     else if (tc.stride_w == 4) wide.push_back((int)i);
     else fast = false;
@@ -424,3 +488,11 @@ extern "C" int mbx_plan_free(mbx_plan* p) {
 }
 
 bool mbx::plan_has_real(const mbx_plan* p) { return p->host.has_real != 0; }
+
+extern "C" int mbx_plan_dict_terms(mbx_ctx* c, const mbx_plan* p, int32_t* nterms) {
+  NOTNULL(c);
+  NOTNULL(p);
+  NOTNULL(nterms);
+  *nterms = p->dict_terms;
+  return MBX_OK;
+}

@@ -17,17 +17,17 @@ using namespace mbx;
 
 // ------------------------------------------------------------ table planes
 
-// Byte-plane slices of one int32 column: the key range
-// on the device, then the planes below the range's constant prefix.  One read
-// of the column and a write of <= 4 bytes per row; synchronous.
-static int slice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
-  const int32_t* src = (const int32_t*)t->cols[(size_t)col].dev;
-  const int64_t pstride = padded_rows(t->nrows, kSliceTileRows);
+// Byte-plane slices of one int32 column of nrows rows -- a table's, or the
+// code column of a dictionary: the key range on the
+// device, then the planes below the range's constant prefix.  One read of the
+// column and a write of <= 4 bytes per row; synchronous.
+static int slice_build_col(mbx_ctx* c, const int32_t* src, int64_t nrows, TSlice& out) {
+  const int64_t pstride = padded_rows(nrows, kSliceTileRows);
   uint32_t* dmm = nullptr;
   if (hipMalloc(&dmm, 2 * sizeof(uint32_t)) != hipSuccess) return fail(MBX_E_NOMEM, "table_slice: scratch");
   uint32_t mm[2] = {~0u, 0u};
   hipError_t e = hipMemcpyAsync(dmm, mm, sizeof(mm), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_slice_minmax(src, t->nrows, dmm, c->stream);
+  if (e == hipSuccess) e = launch_slice_minmax(src, nrows, dmm, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(mm, dmm, sizeof(mm), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   hipFree(dmm);
@@ -44,14 +44,13 @@ static int slice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
     (void)hipGetLastError();
     return fail(MBX_E_NOMEM, "table_slice: %zu bytes", bytes);
   }
-  e = launch_slice_build(src, t->nrows, sl.first, pstride, sl.dev, c->stream);
+  e = launch_slice_build(src, nrows, sl.first, pstride, sl.dev, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
     hipFree(sl.dev);
     return fail(MBX_E_DEVICE, "table_slice: %s", hipGetErrorString(e));
   }
-  if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
-  t->slices[(size_t)col] = sl;
+  out = sl;
   return MBX_OK;
 }
 
@@ -61,22 +60,20 @@ static int64_t bit_pstride(int64_t nrows) { return padded_rows(nrows, kBitTileRo
 // Bit planes of a sliced column, over the slice's key range: one more read of
 // the column and a write of <= 1 byte per row; synchronous.  Adds to the
 // slice and drops nothing, so slice_gen stays.
-static int bitslice_build_col(mbx_ctx* c, const mbx_table* t, int32_t col) {
-  TSlice& sl = t->slices[(size_t)col];
+static int bitslice_build_col(mbx_ctx* c, const int32_t* src, int64_t nrows, TSlice& sl) {
   const mbx::BitRange br = mbx::bit_range_of(sl.kmin, sl.kmax);
   if (br.w == 0) {  // a constant column: every bound is decided on the host
     sl.bit_w = 0;
     return MBX_OK;
   }
-  const int64_t pstride = bit_pstride(t->nrows);
+  const int64_t pstride = bit_pstride(nrows);
   const size_t bytes = (size_t)br.w * (size_t)pstride * sizeof(uint32_t);
   uint32_t* dev = nullptr;
   if (hipMalloc(&dev, bytes) != hipSuccess) {
     (void)hipGetLastError();
     return fail(MBX_E_NOMEM, "table bit planes: %zu bytes", bytes);
   }
-  hipError_t e = launch_bitslice_build((const int32_t*)t->cols[(size_t)col].dev, t->nrows, br.base, br.h, br.w,
-                                       pstride, dev, c->stream);
+  hipError_t e = launch_bitslice_build(src, nrows, br.base, br.h, br.w, pstride, dev, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
     hipFree(dev);
@@ -143,9 +140,20 @@ extern "C" int mbx_table_slice(mbx_ctx* c, mbx_table* t, const int32_t* cols, in
       dropped = true;
     }
   }
+  // ncols = 0 drops the planes of the dictionaries' code columns too (they
+  // live in the dictionary, which plans share: freed here, after the sync)
+  for (const auto& d : t->dicts)
+    if (ncols == 0 && d && d->slice.stored) {
+      hipFree(d->slice.dev);
+      hipFree(d->slice.bdev);
+      d->slice = TSlice();
+      dropped = true;
+    }
   if (dropped) t->slice_gen++;  // plans bound to the dropped slices scan the columns from now on
   for (int32_t k = 0; k < ncols; k++)
-    if (!t->slices[(size_t)cols[k]].stored && (rc = slice_build_col(c, t, cols[k]))) return rc;
+    if (!t->slices[(size_t)cols[k]].stored &&
+        (rc = slice_build_col(c, (const int32_t*)t->cols[(size_t)cols[k]].dev, t->nrows, t->slices[(size_t)cols[k]])))
+      return rc;
   return MBX_OK;
 }
 
@@ -162,8 +170,9 @@ extern "C" int mbx_table_slice_info(const mbx_table* t, int32_t col, int32_t* st
 
 // Sliced COUNT scan eligibility: 1..4 terms `int32 column OP int literal`
 // (either operand order: the range form normalises both) over <= 4 columns,
-// any CNF shape.  Never-true int terms are dropped by compile_into; a plan
-// that keeps no term references no column and stays on the column scan.
+// any CNF shape; a dictionary's code column (kCodeCol) is an int32 column.
+// Never-true int terms are dropped by compile_into; a plan that keeps no term
+// references no column and stays on the column scan.
 static bool slice_eligible(const mbx_plan* p) {
   const KPlan& h = p->host;
   if (!p->all_literal || h.has_real || p->ctx->tune.force_generic) return false;
@@ -172,7 +181,7 @@ static bool slice_eligible(const mbx_plan* p) {
   for (int32_t i = 0; i < h.nterms; i++)
     if (h.terms[i].kind != kInt || h.terms[i].rhs >= 0) return false;
   for (int32_t col : p->slot_col)
-    if (p->t->cols[(size_t)col].attr_type != MBX_ATTR_INTEGER) return false;
+    if (plan_col(p, col).attr_type != MBX_ATTR_INTEGER) return false;
   return true;
 }
 
@@ -250,7 +259,7 @@ static bool bind_bits(mbx_ctx* c, mbx_plan* p) {
   int32_t depth[kSliceMaxTerms] = {0, 0, 0, 0}, planes = 0;
   for (int32_t i = 0; i < h.nterms; i++) {
     const KTerm& kt = h.terms[i];
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
+    const TSlice& sl = plan_slice(p, p->slot_col[(size_t)kt.lhs]);
     const uint32_t klo = (uint32_t)kt.rlo ^ 0x80000000u, khi = klo + kt.rspan;  // as bind_slices
     const int32_t w = mbx::bit_range_of(sl.kmin, sl.kmax).w;
     int32_t slo, shi, dlo, dhi;
@@ -265,8 +274,11 @@ static bool bind_bits(mbx_ctx* c, mbx_plan* p) {
   for (int32_t i = 0; i < h.nterms; i++) {
     if (depth[i] == 0) continue;  // no plane of its column is read for this term
     const int32_t col = p->slot_col[(size_t)h.terms[i].lhs];
-    if (t->slices[(size_t)col].bit_w < 0 && (c->capturing || bitslice_build_col(c, t, col))) return false;
-    bp.terms[i].planes = t->slices[(size_t)col].bdev;
+    TSlice& sl = plan_slice(p, col);
+    if (sl.bit_w < 0 &&
+        (c->capturing || bitslice_build_col(c, (const int32_t*)plan_col(p, col).dev, t->nrows, sl)))
+      return false;
+    bp.terms[i].planes = sl.bdev;
   }
   slice_conjuncts(h, bp.cmask, &bp.nconj, &bp.never);
   if (!upload_binding(p, kFormBits, &bp, sizeof(bp), planes)) return false;
@@ -281,8 +293,9 @@ void mbx::bind_planes(mbx_ctx* c, mbx_plan* p) {
   const mbx_table* t = p->t;
   if (t->slices.size() != t->cols.size()) t->slices.resize(t->cols.size());
   for (int32_t col : p->slot_col)
-    if (!t->slices[(size_t)col].stored) {
-      if (c->capturing || slice_build_col(c, t, col)) return;
+    if (!plan_slice(p, col).stored) {
+      if (c->capturing || slice_build_col(c, (const int32_t*)plan_col(p, col).dev, t->nrows, plan_slice(p, col)))
+        return;
     }
   if (c->tune.auto_bitslice && bind_bits(c, p)) return;
   const KPlan& h = p->host;
@@ -292,14 +305,14 @@ void mbx::bind_planes(mbx_ctx* c, mbx_plan* p) {
   sp.nterms = h.nterms;
   sp.pstride = padded_rows(t->nrows, kSliceTileRows);
   for (int32_t s = 0; s < sp.ncols; s++) {
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)s]];
+    const TSlice& sl = plan_slice(p, p->slot_col[(size_t)s]);
     sp.planes[s] = sl.dev;
     sp.first[s] = sl.first;
   }
   for (int32_t i = 0; i < h.nterms; i++) {
     const KTerm& kt = h.terms[i];
     KSliceTerm& st = sp.terms[i];
-    const TSlice& sl = t->slices[(size_t)p->slot_col[(size_t)kt.lhs]];
+    const TSlice& sl = plan_slice(p, p->slot_col[(size_t)kt.lhs]);
     st.klo = (uint32_t)kt.rlo ^ 0x80000000u;
     st.khi = st.klo + kt.rspan;  // int_range_of: lo <= hi as ints, no wrap
     int32_t slo, shi, dlo, dhi;

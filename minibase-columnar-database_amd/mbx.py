@@ -121,7 +121,14 @@ EXPORTS = [
     # include/mbx_index.h
     "mbx_index_build", "mbx_index_info", "mbx_index_free", "mbx_index_key_ranges", "mbx_index_probe",
     "mbx_index_scan_open", "mbx_index_scan_positions",
+    # include/mbx_dict.h
+    "mbx_table_dict", "mbx_table_dict_info", "mbx_table_dict_values", "mbx_table_dict_codes",
+    "mbx_dict_term_range", "mbx_plan_dict_terms",
 ]
+# symbols lib() may find missing: empty, except in a tool that loads an older
+# libmbx.so to measure a baseline (tools/bench_dict.py --lib)
+OPTIONAL_EXPORTS = set()
+DICT_MAX_VALUES = 1 << 20  # MBX_DICT_MAX_VALUES
 JOIN_BMJ, JOIN_NLJ = 0, 1
 JOIN_FORM_AUTO, JOIN_FORM_MATRIX, JOIN_FORM_EQUI = 0, 1, 2
 SORT_ASC, SORT_DSC = 0, 1
@@ -323,8 +330,17 @@ def lib():
         "mbx_index_probe": ([V, V, P(Cnf), P(I32), P(I64)], ctypes.c_int),
         "mbx_index_scan_open": ([V, V, V, P(Cnf), P(I32), I32, P(V)], ctypes.c_int),
         "mbx_index_scan_positions": ([V, V, V, P(Cnf), V, I64, P(I64)], ctypes.c_int),
+        "mbx_table_dict": ([V, V, P(I32), I32], ctypes.c_int),
+        "mbx_table_dict_info": ([V, I32, P(I64), P(I32), P(I32)], ctypes.c_int),
+        "mbx_table_dict_values": ([V, V, I32, I64, I64, V], ctypes.c_int),
+        "mbx_table_dict_codes": ([V, V, I32, I64, I64, V], ctypes.c_int),
+        "mbx_dict_term_range": ([V, I64, I32, I32, ctypes.c_char_p, I32, I32, P(I32), P(I32), P(I32)],
+                                ctypes.c_int),
+        "mbx_plan_dict_terms": ([V, V, P(I32)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
+        if name in OPTIONAL_EXPORTS and not hasattr(L, name):
+            continue
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res
@@ -540,6 +556,46 @@ class Context:
         k = ScanClass()
         _chk(lib().mbx_plan_scan_class(self.h, plan.h, mode, agg_col, ctypes.byref(k)))
         return {name: getattr(k, name) for name, _ in ScanClass._fields_}
+
+    def table_dict(self, table, cols):
+        """mbx_table_dict: an order-preserving dictionary of each named char(n)
+        column -- its sorted distinct values and an int32 code column -- which
+        plans compiled afterwards read instead of the strings (same results,
+        4 bytes per row or fewer); naming a column again rebuilds it, cols = []
+        drops every dictionary (a snapshot: rebuild after rewriting wrapped
+        columns; plans compiled on it keep it alive)."""
+        arr = (ctypes.c_int32 * len(cols))(*cols) if cols else None
+        _chk(lib().mbx_table_dict(self.h, table.h, arr, len(cols)))
+
+    def dict_info(self, table, col):
+        """mbx_table_dict_info: (distinct values, byte planes, bit planes) of
+        column `col`'s dictionary and its code column; values 0: no dictionary."""
+        v, sp, b = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        _chk(lib().mbx_table_dict_info(table.h, col, ctypes.byref(v), ctypes.byref(sp), ctypes.byref(b)))
+        return v.value, sp.value, b.value
+
+    def dict_values(self, table, col, start=0, n=None):
+        """mbx_table_dict_values: the dictionary's values ascending, uint8 [n, size]."""
+        size = table.descs[col][1]
+        if n is None:
+            n = self.dict_info(table, col)[0] - start
+        out = np.zeros((n, size), dtype=np.uint8)
+        _chk(lib().mbx_table_dict_values(self.h, table.h, col, start, n, out.ctypes.data if n else None))
+        return out
+
+    def dict_codes(self, table, col, row_start=0, n=None):
+        """mbx_table_dict_codes: the int32 codes of rows row_start .. row_start + n - 1."""
+        if n is None:
+            n = table.nrows - row_start
+        out = np.zeros(n, dtype=np.int32)
+        _chk(lib().mbx_table_dict_codes(self.h, table.h, col, row_start, n, out.ctypes.data if n else None))
+        return out
+
+    def plan_dict_terms(self, plan):
+        """mbx_plan_dict_terms: the terms of the plan that read a code column."""
+        n = ctypes.c_int32()
+        _chk(lib().mbx_plan_dict_terms(self.h, plan.h, ctypes.byref(n)))
+        return n.value
 
     def bitslice_info(self, table, col):
         """mbx_table_bitslice_info: the bit planes column `col` keeps (0: none)."""
@@ -947,6 +1003,22 @@ def index_key_ranges(key_desc, cnf, key_fld=1):
     n = ctypes.c_int32()
     _chk(lib().mbx_index_key_ranges(ctypes.byref(d), ctypes.byref(c), key_fld, out, cap, ctypes.byref(n)))
     return [(out[i].lo_cond, out[i].lo_strict, out[i].hi_cond, out[i].hi_strict) for i in range(n.value)]
+
+
+def dict_term_range(values, op, lit, lit_on_left=False, size=None):
+    """mbx_dict_term_range: (lo, hi, neg) -- the codes for which `value OP lit`
+    holds (lit_on_left: `lit OP value`) over the ascending distinct values
+    (uint8 [n, size]): the term holds iff (lo <= code <= hi) != neg.  lit: bytes
+    of modified UTF-8, or a str.  Needs no GPU."""
+    v = np.ascontiguousarray(values, dtype=np.uint8)
+    if size is None:
+        size = v.shape[1]
+    n = v.size // size if size > 0 else 0
+    b = java_mutf8(lit)
+    lo, hi, neg = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _chk(lib().mbx_dict_term_range(v.ctypes.data if n else None, n, size, op, b, len(b), 1 if lit_on_left else 0,
+                                   ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(neg)))
+    return lo.value, hi.value, bool(neg.value)
 
 
 def bitslice_range(kmin, kmax):

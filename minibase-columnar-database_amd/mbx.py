@@ -124,11 +124,17 @@ EXPORTS = [
     # include/mbx_dict.h
     "mbx_table_dict", "mbx_table_dict_info", "mbx_table_dict_values", "mbx_table_dict_codes",
     "mbx_dict_term_range", "mbx_plan_dict_terms",
+    # include/mbx_group.h
+    "mbx_group_by", "mbx_scan_group", "mbx_groups_info", "mbx_groups_fetch", "mbx_groups_free",
+    "mbx_group_table_bytes", "mbx_group_lds_keys", "mbx_group_by_async", "mbx_group_table_decode",
 ]
 # symbols lib() may find missing: empty, except in a tool that loads an older
 # libmbx.so to measure a baseline (tools/bench_dict.py --lib)
 OPTIONAL_EXPORTS = set()
 DICT_MAX_VALUES = 1 << 20  # MBX_DICT_MAX_VALUES
+GROUP_MAX_KEYS = 1 << 20   # MBX_GROUP_MAX_KEYS
+GROUP_FORM_AUTO, GROUP_FORM_LDS, GROUP_FORM_GLOBAL = 0, 1, 2
+ATTR_NULL = 4              # MBX_ATTR_NULL: a COUNT-only grouping's agg_type
 JOIN_BMJ, JOIN_NLJ = 0, 1
 JOIN_FORM_AUTO, JOIN_FORM_MATRIX, JOIN_FORM_EQUI = 0, 1, 2
 SORT_ASC, SORT_DSC = 0, 1
@@ -337,6 +343,15 @@ def lib():
         "mbx_dict_term_range": ([V, I64, I32, I32, ctypes.c_char_p, I32, I32, P(I32), P(I32), P(I32)],
                                 ctypes.c_int),
         "mbx_plan_dict_terms": ([V, V, P(I32)], ctypes.c_int),
+        "mbx_group_by": ([V, V, V, I32, I32, I32, I32, I32, P(V)], ctypes.c_int),
+        "mbx_scan_group": ([V, V, I32, I32, P(V)], ctypes.c_int),
+        "mbx_groups_info": ([V, P(I64), P(I32), P(I32), P(I64), P(I32)], ctypes.c_int),
+        "mbx_groups_fetch": ([V, V, I64, I64, V, V], ctypes.c_int),
+        "mbx_groups_free": ([V], ctypes.c_int),
+        "mbx_group_table_bytes": ([I64, P(I64)], ctypes.c_int),
+        "mbx_group_lds_keys": ([I32, P(I64)], ctypes.c_int),
+        "mbx_group_by_async": ([V, V, V, I32, I32, I32, I32, I32, V], ctypes.c_int),
+        "mbx_group_table_decode": ([V, I64, I32, I32, V, V, I64, P(I64), P(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name in OPTIONAL_EXPORTS and not hasattr(L, name):
@@ -596,6 +611,54 @@ class Context:
         n = ctypes.c_int32()
         _chk(lib().mbx_plan_dict_terms(self.h, plan.h, ctypes.byref(n)))
         return n.value
+
+    # -- grouped aggregates (include/mbx_group.h) --------------------------
+    @staticmethod
+    def _group_domain(domain):
+        # None: measured (key_lo > key_hi); ignored for a dictionary key
+        return (1, 0) if domain is None else (int(domain[0]), int(domain[1]))
+
+    def _groups(self, h, key_col):
+        try:
+            n, code, at = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+            outside, form = ctypes.c_int64(), ctypes.c_int32()
+            _chk(lib().mbx_groups_info(h, ctypes.byref(n), ctypes.byref(code), ctypes.byref(at), ctypes.byref(outside),
+                                       ctypes.byref(form)))
+            keys = np.zeros(max(1, n.value), dtype=np.int32)
+            aggs = (Agg * max(1, n.value))()
+            _chk(lib().mbx_groups_fetch(self.h, h, 0, n.value, keys.ctypes.data, aggs))
+            return Groups(keys[:n.value], aggs, n.value, bool(code.value), at.value, outside.value, form.value, key_col)
+        finally:
+            lib().mbx_groups_free(h)
+
+    def group_by(self, table, key_col, agg_col=None, sel=None, domain=None, form=GROUP_FORM_AUTO):
+        """mbx_group_by: COUNT / SUM / MIN / MAX of column agg_col (None: COUNT
+        only) per key of key_col -- an int column, or a char(n) column with a
+        dictionary (grouped by code) -- over the rows of `sel` (None: every row
+        not marked deleted).  domain = (key_lo, key_hi) states an int key's
+        domain (rows outside it are counted in .outside), None measures it.
+        Returns a Groups."""
+        lo, hi = self._group_domain(domain)
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_group_by(self.h, table.h, None if sel is None else sel.h, key_col, lo, hi,
+                                -1 if agg_col is None else agg_col, form, ctypes.byref(h)))
+        return self._groups(h, key_col)
+
+    def scan_group(self, plan, key_col, agg_col=None):
+        """mbx_scan_group: the plan's BitSet scan, then group_by over it with a
+        measured domain."""
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_scan_group(self.h, plan.h, key_col, -1 if agg_col is None else agg_col, ctypes.byref(h)))
+        return self._groups(h, key_col)
+
+    def group_by_async(self, table, key_col, dev_table, agg_col=None, sel=None, domain=None, form=GROUP_FORM_AUTO):
+        """mbx_group_by_async: the table init and the grouping launch enqueued
+        on self.stream into dev_table (a device pointer as int: group_table_bytes
+        of the domain's width, 128-byte aligned); capturable.  An int key needs
+        a stated domain."""
+        lo, hi = self._group_domain(domain)
+        _chk(lib().mbx_group_by_async(self.h, table.h, None if sel is None else sel.h, key_col, lo, hi,
+                                      -1 if agg_col is None else agg_col, form, dev_table))
 
     def bitslice_info(self, table, col):
         """mbx_table_bitslice_info: the bit planes column `col` keeps (0: none)."""
@@ -1019,6 +1082,66 @@ def dict_term_range(values, op, lit, lit_on_left=False, size=None):
     _chk(lib().mbx_dict_term_range(v.ctypes.data if n else None, n, size, op, b, len(b), 1 if lit_on_left else 0,
                                    ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(neg)))
     return lo.value, hi.value, bool(neg.value)
+
+
+class Groups:
+    """The groups of one group_by / scan_group / group_table_decode, ascending
+    by key: keys (int32: the int values, or dictionary codes when key_is_code),
+    count / sum / min / max arrays (sum int64 or float64, min / max int32 or
+    float32; None for a COUNT-only grouping), outside (selected rows outside a
+    stated domain) and form (GROUP_FORM_LDS / _GLOBAL; 0: nothing ran)."""
+
+    def __init__(self, keys, aggs, n, key_is_code, agg_type, outside, form, key_col=None):
+        self.key_col = key_col
+        self.keys, self.key_is_code, self.agg_type, self.outside, self.form = keys, key_is_code, agg_type, outside, form
+        self.count = np.array([aggs[i].count for i in range(n)], dtype=np.int64)
+        self.sum = self.min = self.max = None
+        if agg_type == INTEGER:
+            self.sum = np.array([aggs[i].isum for i in range(n)], dtype=np.int64)
+            self.min = np.array([aggs[i].imin for i in range(n)], dtype=np.int32)
+            self.max = np.array([aggs[i].imax for i in range(n)], dtype=np.int32)
+        elif agg_type == REAL:
+            self.sum = np.array([aggs[i].fsum for i in range(n)], dtype=np.float64)
+            self.min = np.array([aggs[i].fmin for i in range(n)], dtype=np.float32)
+            self.max = np.array([aggs[i].fmax for i in range(n)], dtype=np.float32)
+
+    def __len__(self):
+        return len(self.keys)
+
+    def values(self, ctx, table):
+        """the groups' key values: the strings (uint8 [n, size]) of a code key
+        through the table's dictionary, else the keys themselves"""
+        if not self.key_is_code:
+            return self.keys
+        return ctx.dict_values(table, self.key_col)[self.keys]
+
+
+def group_table_bytes(width):
+    """mbx_group_table_bytes: bytes of the dense table of `width` slots.  Needs no GPU."""
+    b = ctypes.c_int64()
+    _chk(lib().mbx_group_table_bytes(int(width), ctypes.byref(b)))
+    return b.value
+
+
+def group_lds_keys(with_value):
+    """mbx_group_lds_keys: the widest domain the LDS form takes.  Needs no GPU."""
+    k = ctypes.c_int64()
+    _chk(lib().mbx_group_lds_keys(1 if with_value else 0, ctypes.byref(k)))
+    return k.value
+
+
+def group_table_decode(host_table, width, key_lo, agg_type, key_is_code=False, key_col=None):
+    """mbx_group_table_decode: the Groups of a host copy (bytes-like / uint8
+    array of group_table_bytes(width)) of a dense table.  Needs no GPU."""
+    buf = np.ascontiguousarray(np.frombuffer(host_table, dtype=np.uint8))
+    n, outside = ctypes.c_int64(), ctypes.c_int64()
+    _chk(lib().mbx_group_table_decode(buf.ctypes.data, int(width), int(key_lo), agg_type, None, None, 0,
+                                      ctypes.byref(n), ctypes.byref(outside)))
+    keys = np.zeros(max(1, n.value), dtype=np.int32)
+    aggs = (Agg * max(1, n.value))()
+    _chk(lib().mbx_group_table_decode(buf.ctypes.data, int(width), int(key_lo), agg_type, keys.ctypes.data, aggs,
+                                      n.value, ctypes.byref(n), ctypes.byref(outside)))
+    return Groups(keys[:n.value], aggs, n.value, key_is_code, agg_type, outside.value, 0, key_col)
 
 
 def bitslice_range(kmin, kmax):

@@ -38,7 +38,7 @@ struct mbx_graph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   int64_t nodes = 0;                            // mbx_graph_info
-  int64_t fused_launches = 0, fused_scans = 0;  // the capture's COUNT chains (Bits1Fuse, mbx_planes.hip)
+  int64_t fused_launches = 0, fused_scans = 0;  // the capture's COUNT chains (Bits1Fuse, mbx_fuse.cpp)
   int64_t plane_groups = 0, shared_scans = 0;   // mbx_graph_plane_groups
   Bits1Replay* replay = nullptr;                // the graph is one COUNT-chain kernel node: that launch, else null
   int32_t form = 0;                             // mbx_graph_set_replay: 0 hipGraphLaunch, 1 the record's launch

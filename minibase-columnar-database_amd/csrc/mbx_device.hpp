@@ -441,7 +441,7 @@ __device__ __forceinline__ void block_reduce_store(Acc a, const ScanLaunch& L) {
   }
 }
 
-// ---- COUNT epilogue of the plane scans (mbx_planes.hip)
+// ---- COUNT epilogue of the plane scans (mbx_slices.hip, mbx_bits.hip, mbx_bits1.hip)
 //
 // A plane kernel's body is one or two round trips to memory, so what follows
 // its last load is on the critical path of every block.  An integer COUNT needs

@@ -585,7 +585,7 @@ hipError_t launch_slice_build(const int32_t* col, int64_t nrows, int32_t first, 
 // rules) becomes one more grid row of the chain's kernel node instead of a node of its own.
 struct Bits1Fuse;
 hipError_t launch_scan_bits(const ScanLaunch& L, const KBitPlan* shallow, hipStream_t s, Bits1Fuse* fuse = nullptr);
-// A context's chain state (mbx_planes.hip), allocated once at mbx_init.  begin: a capture opens
+// A context's chain state (mbx_fuse.cpp), allocated once at mbx_init.  begin: a capture opens
 // (on: the graph_fuse_counts knob) -- no chain, counters zeroed; end: the capture is over -- no
 // chain; what the capture fused: launches that hold more than one scan, and the scans in them
 Bits1Fuse* bits1_fuse_new();

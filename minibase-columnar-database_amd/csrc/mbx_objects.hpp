@@ -121,7 +121,7 @@ struct mbx_ctx {
   int32_t* dnan = nullptr;       // async scans: [0] last, [1] sticky until mbx_sync; sync scans: [2]
   uint32_t* ticket = nullptr;   // in-launch finalize tickets (always 0 between launches): kMaxFuse areas of
                                 // kTicketWords; every launch takes area 0, query j of a fused batch area j
-  mbx::Bits1Fuse* fuse = nullptr;  // chain of captured shallow COUNT launches (mbx_planes.hip), owned
+  mbx::Bits1Fuse* fuse = nullptr;  // chain of captured shallow COUNT launches (mbx_fuse.cpp), owned
   int64_t* ids_scratch = nullptr;  // positions for a gather whose caller wants no positions
   int64_t ids_cap = 0;
   int64_t* stamps = nullptr;    // diagnostic per-block stamps (select_dbg bit 3)

@@ -1,4 +1,4 @@
-// mbx_planes.cpp -- host side of the plane scans (mbx_planes.hip): byte-plane
+// mbx_planes.cpp -- host side of the plane scans (mbx_slices.hip, mbx_bits.hip, mbx_bits1.hip): byte-plane
 // slices and bit planes of int32 columns (mbx_table_slice), the binding of a
 // plan's COUNT scans (and a bit-bound plan's BitSet scans) to them at
 // mbx_plan_compile, and the geometry and launch of a bound plan's scans.  The

@@ -1,6 +1,6 @@
 // mbx_scan.cpp -- the predicate scans of the C-ABI (include/mbx.h): COUNT,
 // BitSet, BitSet + positions and aggregate, synchronous and *_async, over the
-// kernels of mbx_scan_*.hip, mbx_select.hip and mbx_planes.hip.
+// kernels of mbx_scan_*.hip, mbx_select.hip, mbx_slices.hip, mbx_bits.hip and mbx_bits1.hip.
 //
 // Owns the launch decision: the grid of a scan (tiles_per_block_for,
 // scan_tiles_per_block), which kernel class and finalize a launch takes

@@ -1,4 +1,4 @@
-// mbx_scan_bits1_body.hpp -- the body of k_scan_bits1 and k_scan_bits1_batch (mbx_planes.hip), included
+// mbx_scan_bits1_body.hpp -- the body of k_scan_bits1 and k_scan_bits1_batch (mbx_bits1.hip), included
 // inside each kernel: NP, DEL, FIN are the kernel's template parameters, P its Bits1Launch record (the
 // kernel argument / record blockIdx.y of the batch), the macro MBX_BITS1_GRID_X the blocks of P's query
 // (a named constant in its place changes k_scan_bits1's code).  No include guard: it is text.

@@ -127,6 +127,9 @@ EXPORTS = [
     # include/mbx_group.h
     "mbx_group_by", "mbx_scan_group", "mbx_groups_info", "mbx_groups_fetch", "mbx_groups_free",
     "mbx_group_table_bytes", "mbx_group_lds_keys", "mbx_group_by_async", "mbx_group_table_decode",
+    # include/mbx_group_sort.h
+    "mbx_group_sort", "mbx_scan_group_sort", "mbx_sorted_groups_info", "mbx_sorted_groups_fetch",
+    "mbx_sorted_groups_free",
 ]
 # symbols lib() may find missing: empty, except in a tool that loads an older
 # libmbx.so to measure a baseline (tools/bench_dict.py --lib)
@@ -352,6 +355,11 @@ def lib():
         "mbx_group_lds_keys": ([I32, P(I64)], ctypes.c_int),
         "mbx_group_by_async": ([V, V, V, I32, I32, I32, I32, I32, V], ctypes.c_int),
         "mbx_group_table_decode": ([V, I64, I32, I32, V, V, I64, P(I64), P(I64)], ctypes.c_int),
+        "mbx_group_sort": ([V, V, V, P(I32), I32, I32, P(V)], ctypes.c_int),
+        "mbx_scan_group_sort": ([V, V, P(I32), I32, I32, P(V)], ctypes.c_int),
+        "mbx_sorted_groups_info": ([V, P(I64), P(I64), P(I32), P(I32), P(I32)], ctypes.c_int),
+        "mbx_sorted_groups_fetch": ([V, V, I64, I64, V, V], ctypes.c_int),
+        "mbx_sorted_groups_free": ([V], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if name in OPTIONAL_EXPORTS and not hasattr(L, name):
@@ -659,6 +667,44 @@ class Context:
         lo, hi = self._group_domain(domain)
         _chk(lib().mbx_group_by_async(self.h, table.h, None if sel is None else sel.h, key_col, lo, hi,
                                       -1 if agg_col is None else agg_col, form, dev_table))
+
+    # -- the sort form of grouped aggregates (include/mbx_group_sort.h) ----
+    def _sorted_groups(self, h, key_cols):
+        try:
+            n, rows, at = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+            pr, pt = ctypes.c_int32(), ctypes.c_int32()
+            _chk(lib().mbx_sorted_groups_info(h, ctypes.byref(n), ctypes.byref(rows), ctypes.byref(at), ctypes.byref(pr),
+                                              ctypes.byref(pt)))
+            pos = np.zeros(max(1, n.value), dtype=np.int64)
+            aggs = (Agg * max(1, n.value))()
+            _chk(lib().mbx_sorted_groups_fetch(self.h, h, 0, n.value, pos.ctypes.data, aggs))
+            return SortedGroups(pos[:n.value], aggs, n.value, at.value, rows.value, (pr.value, pt.value), key_cols)
+        finally:
+            lib().mbx_sorted_groups_free(h)
+
+    @staticmethod
+    def _key_cols(key_cols):
+        cols = [int(k) for k in key_cols]
+        return cols, (ctypes.c_int32 * max(1, len(cols)))(*cols)
+
+    def group_sort(self, table, key_cols, agg_col=None, sel=None):
+        """mbx_group_sort: COUNT / SUM / MIN / MAX of column agg_col (None:
+        COUNT only) per distinct value of the key columns -- int or char(n), no
+        dictionary, any domain -- over the rows of `sel` (None: every row not
+        marked deleted).  Returns a SortedGroups."""
+        cols, arr = self._key_cols(key_cols)
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_group_sort(self.h, table.h, None if sel is None else sel.h, arr, len(cols),
+                                  -1 if agg_col is None else agg_col, ctypes.byref(h)))
+        return self._sorted_groups(h, cols)
+
+    def scan_group_sort(self, plan, key_cols, agg_col=None):
+        """mbx_scan_group_sort: the plan's BitSet scan, then group_sort over it."""
+        cols, arr = self._key_cols(key_cols)
+        h = ctypes.c_void_p()
+        _chk(lib().mbx_scan_group_sort(self.h, plan.h, arr, len(cols), -1 if agg_col is None else agg_col,
+                                       ctypes.byref(h)))
+        return self._sorted_groups(h, cols)
 
     def bitslice_info(self, table, col):
         """mbx_table_bitslice_info: the bit planes column `col` keeps (0: none)."""
@@ -1114,6 +1160,34 @@ class Groups:
         if not self.key_is_code:
             return self.keys
         return ctx.dict_values(table, self.key_col)[self.keys]
+
+
+class SortedGroups:
+    """The groups of one group_sort / scan_group_sort, ascending by key (the
+    first key column the most significant): first_positions (int64: the global
+    position of each group's first row), count / sum / min / max arrays typed
+    as in Groups (None for a COUNT-only grouping), rows (the selected rows) and
+    passes (the sort's radix passes run, of how many)."""
+
+    def __init__(self, first_positions, aggs, n, agg_type, rows, passes, key_cols):
+        self.first_positions, self.agg_type, self.rows, self.passes = first_positions, agg_type, rows, passes
+        self.key_cols = list(key_cols)
+        # one view of the mbx_agg array: there may be as many groups as rows
+        a = np.frombuffer(aggs, dtype=np.dtype(Agg), count=n) if n else np.zeros(0, dtype=np.dtype(Agg))
+        self.count = a["count"].copy()
+        self.sum = self.min = self.max = None
+        if agg_type == INTEGER:
+            self.sum, self.min, self.max = a["isum"].copy(), a["imin"].copy(), a["imax"].copy()
+        elif agg_type == REAL:
+            self.sum, self.min, self.max = a["fsum"].copy(), a["fmin"].copy(), a["fmax"].copy()
+
+    def __len__(self):
+        return len(self.first_positions)
+
+    def keys(self, ctx, table):
+        """the groups' key values, one array per key column: a gather of the
+        first rows"""
+        return ctx.gather(table, self.first_positions, self.key_cols)
 
 
 def group_table_bytes(width):
